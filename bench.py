@@ -2,14 +2,22 @@
 (1M mixed cron rules x 24 h horizon, UTC) per MI355X, weak-scaled over
 job-ID-range shards at N > 1.
 
-  python bench.py [--gpus N] [--steps K] [--warmup W] [--workload W]
+  python bench.py [--gpus N] [--steps K] [--warmup W] [--workload W] [--full] [--dump-outputs DIR]
+
+A plain run sets up, warms up, times the K steps and prints the line.
+`--full` adds everything else measured or checked around the timed region:
+the oracle check of the timed result (`verified`, `verify`), the poisoned
+result buffers, the CPU baseline, the per-phase breakdown, the store ceiling,
+the end-to-end line and, at N > 1, the verified gather.  `--dump-outputs DIR`
+writes the last timed step's result as DIR/<name>.npy (see dump_outputs).
+
   (N > 1: one rank per GPU over RCCL.  Run under torch.distributed.run, or
   alone: `--gpus N` then starts torch.distributed.run with N ranks of the same
   command as a child process, before this process touches the GPU, and
   forwards rank 0's JSON line and the child's exit status.  A WORLD_SIZE that
   differs from --gpus is refused.)
 
-At N > 1 every workload ends, after its timed region, with one verified
+At N > 1 with `--full` every workload ends, after its timed region, with one verified
 time-ordered per-node gather (`verify.gather`): a small pernode-shaped window
 gathered on rank 0 in many chunks under a small byte budget (split nodes
 included) -- through the library's RCCL communicator
@@ -191,7 +199,23 @@ def main():
     ap.add_argument("--diagnostic", action="store_true",
                     help="allow the diagnostic library / CG_WRITE_* CG_NODE_* switches (the line is "
                          "then marked diagnostic and is not a headline)")
+    ap.add_argument("--full", action="store_true",
+                    help="beside the timed steps, everything else the benchmark measures or checks: the "
+                         "oracle check of the timed result (--verify-sample), poisoned result buffers, the "
+                         "CPU baseline (--cpu-sample), the per-phase breakdown, the store ceiling, the "
+                         "end-to-end line, the verified gather at N > 1")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what the last timed step left for its caller as "
+                         "DIR/<name>.npy (float64; seeded samples of the large arrays)")
     args = ap.parse_args()
+    if not args.full:
+        # a plain run: set up, warm up, time the steps, dump, print the line
+        if args.cpu_sample or args.verify_sample != ap.get_default("verify_sample"):
+            log("bench.py: --cpu-sample / --verify-sample take effect with --full only")
+        args.cpu_sample = 0
+        args.verify_sample = 0
+    if args.dump_outputs and args.workload in ("parse", "dispatch"):
+        ap.error("--dump-outputs applies to the expansion workloads (config2, pernode, config3, config4)")
 
     if args.workload == "parse":  # host-only: no GPU, no ranks
         print(json.dumps(parse_line(args)), flush=True)
@@ -546,7 +570,7 @@ def main():
             return [(d_time, n_ev, 8), (d_rule, n_ev, 4)]
         _, d_times, n_ev = eng.result_device()
         return [(d_times, n_ev, 8)]
-    if wl != "dispatch":
+    if args.full and wl != "dispatch":
         for ptr, n_ev, w in result_buffers():
             eng.fill(ptr, n_ev * w, 0xFF)
     # per-node pipelined steps: every timed step checks one seeded window (its
@@ -597,7 +621,7 @@ def main():
     # oracle (outside the timed region): a step that skipped work would fail.
     verify = None
     unwritten = None
-    if wl != "dispatch":  # poisoned words the timed steps left unwritten (must be 0)
+    if args.full and wl != "dispatch":  # poisoned words the timed steps left unwritten (must be 0)
         unwritten = sum(eng.count_value(ptr, n_ev, w, -1) for ptr, n_ev, w in result_buffers())
     if args.verify_sample > 0 and wl != "dispatch":
         tv = time.perf_counter()
@@ -623,7 +647,11 @@ def main():
         verify["verified_all_ranks"] = bool(ok.item())
         log(f"[rank {rank}] verify: {verify}")
 
-    if world > 1 and not args.no_gather_check:
+    dumped = None
+    if args.dump_outputs:
+        dumped = dump_outputs(eng, args.dump_outputs, rank, R, n_nodes if pn else 0)
+
+    if args.full and world > 1 and not args.no_gather_check:
         # the multi-rank exchange itself, verified (outside the timed region)
         g = gather_check(eng, dist, world, rank, backend, utc, args.zone, t0, dev, cdev,
                          restore_order=_cg.NODE_ORDER_TIME if (pn and args.time_order) else _cg.NODE_ORDER_RULE)
@@ -634,7 +662,7 @@ def main():
             verify["gather"] = g
             verify["verified_all_ranks"] = verify["verified_all_ranks"] and g["verified"]
 
-    if lean:
+    if lean and args.full:
         # per-phase breakdown of a few untimed steps (events between phases)
         eng.set_phase_timing(2)
         phases = []
@@ -646,7 +674,7 @@ def main():
         kts = [[ph[0], ph[1], ph[2], k[3], ph[4], ph[5]] for k in kts]
 
     e2e = None
-    if wl == "config2" and rank == 0:
+    if args.full and wl == "config2" and rank == 0:
         # end to end, outside the timed region: H2D of the
         # packed specs, the expansion, D2H of the rule-major CSR into pinned
         # host memory (the host parse is reported by the CPU baseline)
@@ -750,7 +778,7 @@ def main():
     # the achievable store rate on this box, beside the nominal peak: a
     # vectorized fill of the same output bytes (outside the timed region)
     ceiling = None
-    if rank == 0 and wl in ("config2", "pernode") and not args.diagnostic:
+    if args.full and rank == 0 and wl in ("config2", "pernode") and not args.diagnostic:
         ceiling = store_ceiling(eng, int(E * 12 if pn else E * 8), torch.device("cuda", local), achieved)
 
     cpu = None
@@ -798,10 +826,12 @@ def main():
                        "cg_expand_per_node_wait at the end of the timed steps; "
                        "per-phase times from the synchronous warmup step, node_write from the timed steps)"
                        if pn_pipelined else "synchronous"),
-        "kernel_ms": {"count": kt[0], "scan": kt[1], "block_map": kt[2], "write_cf": kt[3],
-                      "write_walk": kt[4], "offsets": kt[5],
-                      "timing": "write_cf: HIP events around it in the timed steps; the other "
-                                "phases from 3 untimed steps with events between all phases"
+        "kernel_ms": {"count": ms_or_none(kt[0]), "scan": ms_or_none(kt[1]), "block_map": ms_or_none(kt[2]),
+                      "write_cf": kt[3], "write_walk": ms_or_none(kt[4]), "offsets": ms_or_none(kt[5]),
+                      "timing": ("write_cf: HIP events around it in the timed steps; the other "
+                                 "phases from 3 untimed steps with events between all phases" if args.full else
+                                 "write_cf: HIP events around it in the timed steps; the other phases "
+                                 "are timed with --full only")
                                 if lean else "HIP events between all phases in the timed steps"},
         "roofline": {
             "bound": "hbm",
@@ -823,12 +853,15 @@ def main():
         "cpu_baseline": cpu,
         "step_wall_ms": {"min": min(step_wall) * 1e3, "p50": float(np.median(step_wall)) * 1e3,
                          "max": max(step_wall) * 1e3},
-        "verified": bool(verify and verify["verified_all_ranks"]),
+        "verified": bool(verify["verified_all_ranks"]) if verify else (False if args.full else None),
         "verify": verify,
+        "full": args.full,
         "library": {"path": os.path.relpath(_cg.LIB_PATH, ROOT), "build_info": build_info},
     }
     if args.diagnostic:
         out["diagnostic"] = {"env": diag_env, "note": "probe/variant run: not a headline"}
+    if dumped is not None:
+        out["dumped_outputs"] = dumped
     if e2e is not None:
         out["end_to_end_rank0"] = e2e
     if pn:
@@ -854,6 +887,76 @@ def main():
     print(json.dumps(out), flush=True)
     if world > 1:
         dist.destroy_process_group()
+
+
+def ms_or_none(x):
+    """A phase time for the JSON line: the library reports -1 for a phase it
+    did not time (cg_set_phase_timing(1))."""
+    return float(x) if x >= 0 else None
+
+
+DUMP_SAMPLE = 2_000_000  # elements of a sampled array (16 MB as float64; at most three such files per rank)
+
+
+def dump_outputs(eng, outdir, rank, n_rules, n_nodes, seed=0x5EED + 123):
+    """`--dump-outputs DIR`: the engine's current result -- what the last timed
+    step left for its caller -- as DIR/<name>.npy in float64 (unix seconds,
+    offsets and rule indices are all exact there).  Rule-major workloads:
+    `offsets` (the CSR offsets of every rule, R + 1) and `times` (the fire
+    times); per-node workloads, the last window of the step: `node_offsets`
+    (N + 1), `node_times` and `node_rules`.  An array longer than DUMP_SAMPLE
+    is written as its elements at DUMP_SAMPLE seeded positions (sorted; the
+    same positions in the event arrays of one result), so two builds' files
+    compare element for element.  Ranks above 0 write <name>.rank<k>.npy."""
+    import numpy as np
+    import torch
+    from cronsun_amd._lib import check, lib
+    os.makedirs(outdir, exist_ok=True)
+    dev = torch.device("cuda", eng.device)
+
+    class _View:
+        def __init__(self, ptr, count, typestr):
+            self.__cuda_array_interface__ = {"shape": (count,), "typestr": typestr,
+                                             "data": (ptr, False), "version": 3}
+
+    def sample(ptr, n, typestr, idx):
+        if n == 0:
+            return np.zeros(0, dtype=np.float64)
+        t = torch.as_tensor(_View(ptr, n, typestr), device=dev)
+        return (t if idx is None else t[idx]).cpu().numpy().astype(np.float64)
+
+    def positions(n, on_device=True):
+        if n <= DUMP_SAMPLE:
+            return None
+        idx = np.sort(np.random.default_rng(seed).integers(0, n, DUMP_SAMPLE))
+        return torch.from_numpy(idx).to(dev) if on_device else idx
+
+    def host_sample(a):
+        idx = positions(len(a), on_device=False)
+        return (a if idx is None else a[idx]).astype(np.float64)
+
+    arrays = {}
+    if n_nodes:
+        _, d_time, d_rule, n_ev = eng.node_result_device()
+        node_off = np.empty(n_nodes + 1, dtype=np.int64)
+        check(lib().cg_node_result_copy(eng._h, node_off.ctypes.data, None, None, 0))
+        n_ev = min(n_ev, int(node_off[-1]))
+        idx = positions(n_ev)
+        arrays["node_offsets"] = host_sample(node_off)
+        arrays["node_times"] = sample(d_time, n_ev, "<i8", idx)
+        arrays["node_rules"] = sample(d_rule, n_ev, "<i4", idx)
+    else:
+        _, d_times, n_ev = eng.result_device()
+        off = np.empty(n_rules + 1, dtype=np.int64)
+        check(lib().cg_result_copy_offsets(eng._h, off.ctypes.data))
+        n_ev = min(n_ev, int(off[-1]))
+        arrays["offsets"] = host_sample(off)
+        arrays["times"] = sample(d_times, n_ev, "<i8", positions(n_ev))
+    suffix = "" if rank == 0 else f".rank{rank}"
+    for name, a in arrays.items():
+        np.save(os.path.join(outdir, f"{name}{suffix}.npy"), a)
+    return {"events": int(n_ev), "sampled": bool(n_ev > DUMP_SAMPLE),
+            "files": {f"{name}{suffix}.npy": int(a.size) for name, a in arrays.items()}}
 
 
 def rank_launch_cmd(gpus, argv, port):
@@ -1079,12 +1182,17 @@ def parse_line(args):
         times.append(time.perf_counter() - t)
     assert (status == 0).all()
     dt = float(np.median(times[max(1, args.warmup):]))
-    O = _oracle()
-    sample = base[:200_000]
-    t = time.perf_counter()
-    for s in sample:
-        O.parse(s)
-    dto = time.perf_counter() - t
+    cpu = None
+    if args.full:
+        O = _oracle()
+        sample = base[:200_000]
+        t = time.perf_counter()
+        for s in sample:
+            O.parse(s)
+        dto = time.perf_counter() - t
+        cpu = {"value": len(sample) / dto, "unit": "specs/s", "cores": 1, "kind": "port",
+               "sample": f"the oracle's parser over the first {len(sample)} specs, one "
+                         f"call per spec through ctypes ({dto:.2f} s)"}
     return {"metric": "cron specs parsed/sec (host batch parser, 10M config-2 specs)",
             "value": n_total / dt, "unit": "specs/s", "n_gpus": 0, "steps": max(1, args.steps),
             "warmup": max(1, args.warmup), "ms_per_step": dt * 1e3, "higher_is_better": True,
@@ -1092,9 +1200,7 @@ def parse_line(args):
             "config": {"workload": "parse: 10M spec strings (the 1M config-2 mix repeated), "
                                    "cg_parse_batch, default options (parser.go:171-183)",
                        "threads": threads, **cpuinfo},
-            "cpu_baseline": {"value": len(sample) / dto, "unit": "specs/s", "cores": 1, "kind": "port",
-                             "sample": f"the oracle's parser over the first {len(sample)} specs, one "
-                                       f"call per spec through ctypes ({dto:.2f} s)"}}
+            "cpu_baseline": cpu}
 
 
 def host_cpus():

@@ -1,5 +1,5 @@
-"""bench.py at N = 2 on one GPU, launched by bench.py itself (`--gpus 2`, no
-external launcher): two ranks over gloo, each expanding its job-ID range of
+"""bench.py at N = 2 on one GPU, launched by bench.py itself (`--gpus 2 --full`,
+no external launcher): two ranks over gloo, each expanding its job-ID range of
 the pernode workload in (time, rule) order, the whole per-node CSR gathered on
 rank 0 every timed step (shard.gather_node_csr, chunked) and, after the timed
 region, the verified time-ordered gather of `verify.gather` (24 nodes against
@@ -21,7 +21,8 @@ def test_bench_two_ranks_gloo_gather():
     env = {k: v for k, v in os.environ.items() if k not in ("WORLD_SIZE", "RANK", "LOCAL_RANK")}
     env["CG_DIST_BACKEND"] = "gloo"
     p = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "2", "--workload", "pernode",
-                        "--time-order", "--gather-node-csr", "--steps", "1", "--warmup", "1", "--verify-sample", "500"],
+                        "--time-order", "--gather-node-csr", "--steps", "1", "--warmup", "1", "--full",
+                        "--verify-sample", "500"],
                        capture_output=True, text=True, timeout=400, env=env, cwd=ROOT)
     assert p.returncode == 0, p.stderr[-4000:]
     lines = [ln for ln in p.stdout.splitlines() if ln.strip().startswith("{")]

@@ -11,7 +11,7 @@ O=gpurun_out/$1
 shift
 mkdir -p "$O"
 export TMPDIR=/tmp
-B="bench.py $* --cpu-sample 0 --verify-sample 0"
+B="bench.py $* --full --cpu-sample 0 --verify-sample 0"
 L=${PMC_LIMIT:-400}
 timeout -k 10 $L rocprofv3 --kernel-trace --stats --output-format csv -d $O/prof_kt -- python3 $B > $O/bench_prof.json 2> $O/kt.err || { tail -5 $O/kt.err; exit 1; }
 timeout -s KILL $L rocprofv3 --pmc FETCH_SIZE --output-format csv -d $O/prof_fetch -- python3 $B > /dev/null 2> $O/fetch.err || { tail -5 $O/fetch.err; exit 1; }

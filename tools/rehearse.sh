@@ -9,5 +9,5 @@ shift 2
 mkdir -p $O
 export CG_DIST_BACKEND=gloo
 timeout -k 10 ${REHEARSE_LIMIT:-600} python -m torch.distributed.run --nnodes=1 --nproc-per-node $N --master-addr 127.0.0.1 \
-  --master-port 29533 bench.py --gpus $N "$@" --cpu-sample 0 > $O/line.json 2> $O/line.err || { tail -30 $O/line.err; exit 1; }
+  --master-port 29533 bench.py --gpus $N "$@" --full --cpu-sample 0 > $O/line.json 2> $O/line.err || { tail -30 $O/line.err; exit 1; }
 python3 tools/line.py $O/line.json

@@ -26,6 +26,6 @@ for spec in "$@"; do
   name=${spec%%,*}; lim=400
   [[ "$spec" == *,* ]] && lim=${spec#*,}
   [ -n "${A[$name]}" ] || { echo "unknown workload $name"; exit 2; }
-  timeout -k 10 $lim python -u bench.py ${A[$name]} > $O/$name.json 2> $O/$name.err || { echo "FAILED $name"; tail -20 $O/$name.err; exit 1; }
+  timeout -k 10 $lim python -u bench.py --full ${A[$name]} > $O/$name.json 2> $O/$name.err || { echo "FAILED $name"; tail -20 $O/$name.err; exit 1; }
   python3 tools/line.py $O/$name.json
 done
