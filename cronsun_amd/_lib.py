@@ -32,6 +32,7 @@ PARSE_STANDARD = 2 | 4 | 8 | 16 | 32 | 128
 
 EXCLUDE_NONE, EXCLUDE_RULE, EXCLUDE_CUMULATIVE = 0, 1, 2
 NODE_ORDER_RULE, NODE_ORDER_TIME = 0, 1  # cg_set_node_order
+CG_FANOUT_AUTO, CG_FANOUT_FILTER, CG_FANOUT_DUE = 0, 1, 2  # cg_dispatcher_set_fanout_path
 INGEST_OK, INGEST_UNMARSHAL, INGEST_INVALID, INGEST_PANIC, INGEST_REPLACED, INGEST_UNSUPPORTED = range(6)
 
 
@@ -141,6 +142,12 @@ def _declare(L):
         "cg_dispatcher_set": ([vp, vp, vp, sz, i64], C.c_int),
         "cg_dispatcher_remove": ([vp, vp, sz], C.c_int),
         "cg_dispatcher_snapshot": ([vp, vp, vp, vp], C.c_int),
+        "cg_dispatcher_bind_rules": ([vp, vp, C.c_int], C.c_int),
+        "cg_dispatcher_fanout": ([vp, P(i64)], C.c_int),
+        "cg_dispatcher_fanout_copy": ([vp, vp, vp, i64], C.c_int),
+        "cg_dispatcher_fanout_range": ([vp, i64, i64, vp], C.c_int),
+        "cg_dispatcher_fanout_device": ([vp, P(vp), P(vp), P(i64)], C.c_int),
+        "cg_dispatcher_set_fanout_path": ([vp, C.c_int], C.c_int),
         "cg_expand": ([vp, vp, vp, i64, i64, P(cg_csr)], C.c_int),
         "cg_count": ([vp, vp, vp, i64, i64, vp, P(i64)], C.c_int),
         "cg_expand_device": ([vp, vp, vp, i64, i64, P(i64)], C.c_int),

@@ -163,8 +163,9 @@ struct cg_ctx {
   // offsets), [6..8] per-node phases (rule->node join, transpose + per-node
   // offsets, k_node_write) of the last per-node call, [9..11] dispatcher
   // wake (scan, due compaction, advance) of the last cg_dispatcher_fire, [12]
-  // the time-order pass of the last cg_node_result_order_by_time
-  float kt[13] = {0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0};
+  // the time-order pass of the last cg_node_result_order_by_time, [13] the
+  // last cg_dispatcher_fanout
+  float kt[14] = {0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0};
   // expansion phase timing: 2 = an event between every phase (kt[0..5]);
   // 1 = events around k_write_cf only (kt[3]; the others read -1).  Each
   // event recorded between two kernels costs 6-12 us of idle GPU on this
@@ -338,6 +339,23 @@ bool async_pending(const cg_ctx* c);
 // wait) / any pending
 int pn_async_drain(cg_ctx* c);
 bool pn_async_pending(const cg_ctx* c);  // an asynchronous expansion not yet waited for
+// the rule->node join of a rule set under an exclude mode, left in the ctx's
+// shared join buffers (rn_off [R+1], rn_nodes / pair_rule [nnz]), and its
+// stable node-major transpose (nt_off [N+1], nt_rule [nnz]; rn_nodes /
+// pair_rule are consumed); c->mu held.  The per-node path caches these buffers
+// by (pn_cache_serial, pn_cache_mode): any other caller clears pn_cache_serial.
+int rule_nodes_locked(cg_ctx* c, const RulesStore& st, int mode, int64_t* nnz_out);
+int transpose_locked(cg_ctx* c, int64_t nnz, int32_t N);
+// The transpose's stable LSD passes (k_rs_hist / k_rs_scatter, 8 bits a pass)
+// over n (key, value) pairs with keys < N, ping-ponging between (k0, v0) and
+// (k1, v1); *in_second: the sorted pairs are in (k1, v1).  hist needs
+// radix_hist_words(n) int32, off one more int64, scan_tmp scan_temp_bytes of
+// that count.  Enqueued on st.
+int64_t radix_hist_words(int64_t n);
+void radix_by_key_enqueue(hipStream_t st, uint32_t* k0, int32_t* v0, uint32_t* k1, int32_t* v1, int64_t n,
+                          int32_t N, int32_t* hist, int64_t* off, void* scan_tmp, bool* in_second);
+// off[v] = first index of the sorted keys with keys[i] >= v, v in [0, N] (k_node_bounds)
+void launch_node_bounds(hipStream_t st, const uint32_t* keys, int64_t n, int32_t N, int64_t* off);
 // time-order tile sort + merge of c->node_time / c->node_rule (windows <= 4096 s;
 // cg_node_order.hip), enqueued on st without a host sync
 // in_mode: what the writer left in c->node_time / c->node_rule -- kInTimes

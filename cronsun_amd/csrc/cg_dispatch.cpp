@@ -15,6 +15,7 @@
 #include <vector>
 
 #include "cg_api_internal.h"
+#include "cg_dispatcher.h"
 
 using namespace cg;
 
@@ -47,121 +48,91 @@ int grow_keep(T** p, size_t used, size_t cap, hipStream_t st) {
 
 }  // namespace
 
-struct cg_dispatcher {
-  cg_ctx* ctx = nullptr;
-  ZoneRules zone;
-  // slots
-  int64_t n = 0;
-  size_t cap = 0;  // slots allocated
-  DSpec* specs = nullptr;
-  int64_t* next = nullptr;
-  int64_t* prev = nullptr;
-  std::vector<uint8_t> live;
-  // wake scratch
-  unsigned long long* due_bits = nullptr;
-  uint32_t* tile_cnt = nullptr;
-  unsigned long long* tile_min = nullptr;
-  int32_t* due = nullptr;
-  DispatchState* st = nullptr;
-  int64_t n_due = 0;
-  // the min over Next, host copy (CG_ZERO_TIME = no entry can fire)
-  int64_t effective = CG_ZERO_TIME;
-  // zone table covering [tab_lo, tab_hi], own buffer (the ctx plan buffer is shared)
-  DBuf<char> tab_dev;
-  PlanArgs pa{};
-  int64_t tab_lo = 1, tab_hi = 0;
-  // staging for set/remove
-  DBuf<int64_t> idx_dev;
-  DBuf<DSpec> src_dev;
+void cg_dispatcher::release() {
+  for (void* p : {(void*)specs, (void*)next, (void*)prev, (void*)due_bits, (void*)tile_cnt,
+                  (void*)tile_min, (void*)due, (void*)st})
+    if (p) (void)hipFree(p);
+  specs = nullptr;
+  next = prev = nullptr;
+  due_bits = nullptr;
+  tile_cnt = nullptr;
+  tile_min = nullptr;
+  due = nullptr;
+  st = nullptr;
+  tab_dev.release();
+  idx_dev.release();
+  src_dev.release();
+  fo.release();
+}
 
-  void release() {
-    for (void* p : {(void*)specs, (void*)next, (void*)prev, (void*)due_bits, (void*)tile_cnt,
-                    (void*)tile_min, (void*)due, (void*)st})
-      if (p) (void)hipFree(p);
-    specs = nullptr;
-    next = prev = nullptr;
-    due_bits = nullptr;
-    tile_cnt = nullptr;
-    tile_min = nullptr;
-    due = nullptr;
-    st = nullptr;
-    tab_dev.release();
-    idx_dev.release();
-    src_dev.release();
-  }
+int cg_dispatcher::ensure_table(int64_t now) {
+  if (now - kBack >= tab_lo && now + kAhead <= tab_hi) return CG_OK;
+  if (now < -(int64_t(1) << 45) || now > (int64_t(1) << 45))
+    return cg_fail(CG_ERANGE, "time outside +-1.1M years");
+  ZoneTable t = build_table(zone, now - kBack, now + kTableSpan);
+  const int32_t zn = int32_t(t.when.size());
+  const size_t o_off = size_t(zn) * 8, bytes = o_off + size_t(zn) * 4 + 16;
+  std::vector<char> h(bytes, 0);
+  std::memcpy(h.data(), t.when.data(), size_t(zn) * 8);
+  std::memcpy(h.data() + o_off, t.off.data(), size_t(zn) * 4);
+  int rc = tab_dev.ensure(bytes);
+  if (rc) return rc;
+  HIPCHK(hipMemcpyAsync(tab_dev.p, h.data(), bytes, hipMemcpyHostToDevice, ctx->st));
+  HIPCHK(hipStreamSynchronize(ctx->st));
+  pa = PlanArgs{};
+  pa.zwhen = reinterpret_cast<const int64_t*>(tab_dev.p);
+  pa.zoff = reinterpret_cast<const int32_t*>(tab_dev.p + o_off);
+  pa.zn = zn;
+  if (plan_lds_bytes(pa) > 60 * 1024) return cg_fail(CG_ERANGE, "zone table too large for LDS");
+  tab_lo = now - kBack;
+  tab_hi = now + kTableSpan;
+  return CG_OK;
+}
 
-  // the zone table for Next walks from `now`
-  int ensure_table(int64_t now) {
-    if (now - kBack >= tab_lo && now + kAhead <= tab_hi) return CG_OK;
-    if (now < -(int64_t(1) << 45) || now > (int64_t(1) << 45))
-      return cg_fail(CG_ERANGE, "time outside +-1.1M years");
-    ZoneTable t = build_table(zone, now - kBack, now + kTableSpan);
-    const int32_t zn = int32_t(t.when.size());
-    const size_t o_off = size_t(zn) * 8, bytes = o_off + size_t(zn) * 4 + 16;
-    std::vector<char> h(bytes, 0);
-    std::memcpy(h.data(), t.when.data(), size_t(zn) * 8);
-    std::memcpy(h.data() + o_off, t.off.data(), size_t(zn) * 4);
-    int rc = tab_dev.ensure(bytes);
-    if (rc) return rc;
-    HIPCHK(hipMemcpyAsync(tab_dev.p, h.data(), bytes, hipMemcpyHostToDevice, ctx->st));
-    HIPCHK(hipStreamSynchronize(ctx->st));
-    pa = PlanArgs{};
-    pa.zwhen = reinterpret_cast<const int64_t*>(tab_dev.p);
-    pa.zoff = reinterpret_cast<const int32_t*>(tab_dev.p + o_off);
-    pa.zn = zn;
-    if (plan_lds_bytes(pa) > 60 * 1024) return cg_fail(CG_ERANGE, "zone table too large for LDS");
-    tab_lo = now - kBack;
-    tab_hi = now + kTableSpan;
-    return CG_OK;
-  }
+int cg_dispatcher::reserve(int64_t want) {
+  const size_t w = size_t(want);
+  if (w <= cap) return CG_OK;
+  const size_t nc = std::max(w, cap * 2);
+  const size_t tiles = (nc + kDispatchTile - 1) / kDispatchTile;
+  int rc;
+  if ((rc = grow_keep(&specs, size_t(n), nc, ctx->st)) ||
+      (rc = grow_keep(&next, size_t(n), nc, ctx->st)) ||
+      (rc = grow_keep(&prev, size_t(n), nc, ctx->st)) ||
+      (rc = grow_keep(&due_bits, 0, tiles * (kDispatchTile / 64), ctx->st)) ||
+      (rc = grow_keep(&tile_cnt, 0, tiles, ctx->st)) ||
+      (rc = grow_keep(&tile_min, 0, tiles, ctx->st)) || (rc = grow_keep(&due, 0, nc, ctx->st)))
+    return rc;
+  if (!st) HIPCHK(hipMalloc(&st, sizeof(DispatchState)));
+  cap = nc;
+  live.resize(nc, 0);
+  return CG_OK;
+}
 
-  // every per-slot array sized together, contents of [0, n) kept
-  int reserve(int64_t want) {
-    const size_t w = size_t(want);
-    if (w <= cap) return CG_OK;
-    const size_t nc = std::max(w, cap * 2);
-    const size_t tiles = (nc + kDispatchTile - 1) / kDispatchTile;
-    int rc;
-    if ((rc = grow_keep(&specs, size_t(n), nc, ctx->st)) ||
-        (rc = grow_keep(&next, size_t(n), nc, ctx->st)) ||
-        (rc = grow_keep(&prev, size_t(n), nc, ctx->st)) ||
-        (rc = grow_keep(&due_bits, 0, tiles * (kDispatchTile / 64), ctx->st)) ||
-        (rc = grow_keep(&tile_cnt, 0, tiles, ctx->st)) ||
-        (rc = grow_keep(&tile_min, 0, tiles, ctx->st)) || (rc = grow_keep(&due, 0, nc, ctx->st)))
-      return rc;
-    if (!st) HIPCHK(hipMalloc(&st, sizeof(DispatchState)));
-    cap = nc;
-    live.resize(nc, 0);
-    return CG_OK;
-  }
+int cg_dispatcher::reset_state() {
+  HIPCHK(hipMemsetAsync(st, 0xFF, sizeof(DispatchState), ctx->st));
+  HIPCHK(hipMemsetAsync(&st->n_due, 0, sizeof(unsigned long long), ctx->st));
+  return CG_OK;
+}
 
-  int reset_state() {
-    HIPCHK(hipMemsetAsync(st, 0xFF, sizeof(DispatchState), ctx->st));
-    HIPCHK(hipMemsetAsync(&st->n_due, 0, sizeof(unsigned long long), ctx->st));
-    return CG_OK;
-  }
+int cg_dispatcher::read_state(DispatchState* h) {
+  HIPCHK(hipMemcpyAsync(h, st, sizeof *h, hipMemcpyDeviceToHost, ctx->st));
+  HIPCHK(hipStreamSynchronize(ctx->st));
+  effective = h->min_key == ~0ull ? CG_ZERO_TIME : int64_t(h->min_key ^ (uint64_t(1) << 63));
+  if (h->stuck != ~0ull)
+    return cg_fail(CG_ERANGE, "entry " + std::to_string(h->stuck) +
+                                  ": Schedule.Next never returns for it (the reference run "
+                                  "loop blocks forever); its Next is left unset");
+  return CG_OK;
+}
 
-  // read the state back; CG_ERANGE if some entry's Next never returns
-  int read_state(DispatchState* h) {
-    HIPCHK(hipMemcpyAsync(h, st, sizeof *h, hipMemcpyDeviceToHost, ctx->st));
-    HIPCHK(hipStreamSynchronize(ctx->st));
-    effective = h->min_key == ~0ull ? CG_ZERO_TIME : int64_t(h->min_key ^ (uint64_t(1) << 63));
-    if (h->stuck != ~0ull)
-      return cg_fail(CG_ERANGE, "entry " + std::to_string(h->stuck) +
-                                    ": Schedule.Next never returns for it (the reference run "
-                                    "loop blocks forever); its Next is left unset");
-    return CG_OK;
-  }
-
-  int recompute_min() {
-    int rc = reset_state();
-    if (rc) return rc;
-    launch_dispatch_min(next, n, st, ctx->st);
-    HIPCHK(hipGetLastError());
-    DispatchState h;
-    return read_state(&h);
-  }
-};
+int cg_dispatcher::recompute_min() {
+  int rc = reset_state();
+  if (rc) return rc;
+  launch_dispatch_min(next, n, st, ctx->st);
+  HIPCHK(hipGetLastError());
+  DispatchState h;
+  return read_state(&h);
+}
 
 extern "C" {
 
@@ -224,6 +195,8 @@ int cg_dispatcher_fire(cg_dispatcher* d, int64_t now, int64_t* n_due, int64_t* e
   (void)hipGetLastError();
   HIPCHK(hipSetDevice(c->device));
   d->n_due = 0;
+  d->wake_valid = true;  // (an empty wake when nothing can fire)
+  d->fo.valid = false;
   *n_due = 0;
   *effective = d->effective;
   if (d->effective == CG_ZERO_TIME) return CG_OK;  // nothing can fire: the loop just sleeps
@@ -295,6 +268,7 @@ int cg_dispatcher_set(cg_dispatcher* d, const int64_t* idx, const cg_schedule* s
   std::lock_guard<std::mutex> g(c->mu);
   (void)hipGetLastError();
   HIPCHK(hipSetDevice(c->device));
+  d->wake_valid = d->fo.valid = false;
   int rc = d->ensure_table(now);
   if (!rc && top > d->n) rc = d->reserve(top);
   if (!rc) rc = d->idx_dev.ensure(k);
@@ -326,6 +300,7 @@ int cg_dispatcher_remove(cg_dispatcher* d, const int64_t* idx, size_t k) {
   std::lock_guard<std::mutex> g(c->mu);
   (void)hipGetLastError();
   HIPCHK(hipSetDevice(c->device));
+  d->wake_valid = d->fo.valid = false;
   int rc = d->idx_dev.ensure(k);
   if (rc) return rc;
   HIPCHK(hipMemcpyAsync(d->idx_dev.p, idx, k * 8, hipMemcpyHostToDevice, c->st));

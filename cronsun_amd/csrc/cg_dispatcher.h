@@ -1,0 +1,82 @@
+// cg_dispatcher.h -- the object behind a cg_dispatcher handle (cg_dispatch.cpp
+// owns the wake; cg_fanout.hip the node fan-out of a wake).
+#pragma once
+#include <vector>
+
+#include "cg_api_internal.h"
+
+// Node fan-out of a wake (cg_fanout.hip): the bound rule set's join and the
+// last result, all owned by the dispatcher.
+struct DispatchFanout {
+  bool bound = false;
+  int32_t N = 0;      // nodes of the bound rule set
+  int64_t R = 0;      // its rules: slot i < R is rule i
+  int64_t nnz = 0;    // (rule, node) pairs of the join
+  int path = CG_FANOUT_AUTO;
+  // rule -> nodes CSR and its stable node-major transpose (rules ascending
+  // within a node)
+  DBuf<int64_t> rn_off, nt_off;
+  DBuf<int32_t> rn_nodes, nt_rule;
+  // result: node_off [N+1], slots [n_pairs]
+  DBuf<int64_t> node_off;
+  DBuf<int32_t> slots;
+  int64_t n_pairs = 0;
+  bool valid = false;  // a result of the last wake is readable
+  // filter path: due pairs per tile of the transpose, their scan
+  DBuf<int32_t> tile_cnt;
+  DBuf<int64_t> tile_base;
+  // due-driven path: degrees of the due slots, their scan, the (node, slot)
+  // pairs in due order and the ping-pong of the sort
+  DBuf<int32_t> deg, key0, key1, val1, hist;
+  DBuf<int64_t> deg_off, hist_off;
+  DBuf<char> scan_tmp;
+  void release() {
+    rn_off.release(); nt_off.release(); rn_nodes.release(); nt_rule.release();
+    node_off.release(); slots.release(); tile_cnt.release(); tile_base.release();
+    deg.release(); key0.release(); key1.release(); val1.release(); hist.release();
+    deg_off.release(); hist_off.release(); scan_tmp.release();
+    bound = valid = false;
+  }
+};
+
+struct cg_dispatcher {
+  cg_ctx* ctx = nullptr;
+  cg::ZoneRules zone;
+  // slots
+  int64_t n = 0;
+  size_t cap = 0;  // slots allocated
+  cg::DSpec* specs = nullptr;
+  int64_t* next = nullptr;
+  int64_t* prev = nullptr;
+  std::vector<uint8_t> live;
+  // wake scratch
+  unsigned long long* due_bits = nullptr;
+  uint32_t* tile_cnt = nullptr;
+  unsigned long long* tile_min = nullptr;
+  int32_t* due = nullptr;
+  cg::DispatchState* st = nullptr;
+  int64_t n_due = 0;
+  // due_bits / due hold the last cg_dispatcher_fire's wake (a set or remove
+  // since may have reallocated them)
+  bool wake_valid = false;
+  // the min over Next, host copy (CG_ZERO_TIME = no entry can fire)
+  int64_t effective = CG_ZERO_TIME;
+  // zone table covering [tab_lo, tab_hi], own buffer (the ctx plan buffer is shared)
+  DBuf<char> tab_dev;
+  cg::PlanArgs pa{};
+  int64_t tab_lo = 1, tab_hi = 0;
+  // staging for set/remove
+  DBuf<int64_t> idx_dev;
+  DBuf<cg::DSpec> src_dev;
+  DispatchFanout fo;
+
+  void release();
+  // the zone table for Next walks from `now`
+  int ensure_table(int64_t now);
+  // every per-slot array sized together, contents of [0, n) kept
+  int reserve(int64_t want);
+  int reset_state();
+  // read the state back; CG_ERANGE if some entry's Next never returns
+  int read_state(cg::DispatchState* h);
+  int recompute_min();
+};

@@ -1111,6 +1111,8 @@ int upload_rules(const cg_rules_in* in, RulesStore* st, hipStream_t s) {
   return cg_hip_check(hipStreamSynchronize(s), "upload rules");  // host arrays may go away
 }
 
+}  // namespace
+
 // builds the rule->node CSR on the device; leaves rn_off/rn_nodes/pair_rule in ctx
 int rule_nodes_locked(cg_ctx* c, const RulesStore& st, int mode, int64_t* nnz_out) {
   if (mode < 0 || mode > 2) return cg_fail(CG_EINVAL, "bad exclude mode");
@@ -1150,6 +1152,30 @@ int rule_nodes_locked(cg_ctx* c, const RulesStore& st, int mode, int64_t* nnz_ou
   return CG_OK;
 }
 
+int64_t radix_hist_words(int64_t n) { return kRsBuckets * ((n + kRsTile - 1) / kRsTile); }
+
+void radix_by_key_enqueue(hipStream_t st, uint32_t* k0, int32_t* v0, uint32_t* k1, int32_t* v1, int64_t n,
+                          int32_t N, int32_t* hist, int64_t* off, void* scan_tmp, bool* in_second) {
+  *in_second = false;
+  if (n <= 0) return;
+  const int64_t nb = (n + kRsTile - 1) / kRsTile;
+  uint32_t *kin = k0, *kout = k1;
+  int32_t *vin = v0, *vout = v1;
+  for (int shift = 0; shift == 0 || (int64_t(1) << shift) < int64_t(N); shift += 8) {
+    hipLaunchKernelGGL(k_rs_hist, dim3(unsigned(nb)), dim3(256), 0, st, kin, n, shift, hist, nb);
+    launch_scan(hist, off, kRsBuckets * nb, scan_tmp, st);
+    hipLaunchKernelGGL(k_rs_scatter, dim3(unsigned(nb)), dim3(256), 0, st, kin, vin, n, shift, off, nb, kout,
+                       vout);
+    std::swap(kin, kout);
+    std::swap(vin, vout);
+    *in_second = !*in_second;
+  }
+}
+
+void launch_node_bounds(hipStream_t st, const uint32_t* keys, int64_t n, int32_t N, int64_t* off) {
+  hipLaunchKernelGGL(k_node_bounds, dim3(gridn(int64_t(N) + 1, 256, 1 << 30)), dim3(256), 0, st, keys, n, N, off);
+}
+
 // Stable transpose of the rule-major pairs (rn_nodes, pair_rule) into node
 // order: nt_rule (rules ascending within a node) and nt_off[N+1].
 int transpose_locked(cg_ctx* c, int64_t nnz, int32_t N) {
@@ -1158,35 +1184,26 @@ int transpose_locked(cg_ctx* c, int64_t nnz, int32_t N) {
   if ((rc = c->nt_rule.ensure(std::max<int64_t>(nnz, 1)))) return rc;
   if ((rc = c->pair_node.ensure(std::max<int64_t>(nnz, 1)))) return rc;
   if ((rc = c->nt_off.ensure(N + 1))) return rc;
-  uint32_t* kin = reinterpret_cast<uint32_t*>(c->rn_nodes.p);
-  int32_t* vin = c->pair_rule.p;
-  uint32_t* kout = reinterpret_cast<uint32_t*>(c->pair_node.p);
-  int32_t* vout = c->nt_rule.p;
   if (nnz > 0) {
-    const int64_t nb = (nnz + kRsTile - 1) / kRsTile;
-    if ((rc = c->rs_hist.ensure(kRsBuckets * nb))) return rc;
-    if ((rc = c->rs_off.ensure(kRsBuckets * nb + 1))) return rc;
-    if ((rc = c->scan_tmp.ensure(std::max(c->scan_tmp.cap, scan_temp_bytes(kRsBuckets * nb))))) return rc;
-    int passes = 0;
-    for (int shift = 0; shift == 0 || (int64_t(1) << shift) < int64_t(N); shift += 8) {
-      hipLaunchKernelGGL(k_rs_hist, dim3(unsigned(nb)), dim3(256), 0, st, kin, nnz, shift, c->rs_hist.p, nb);
-      launch_scan(c->rs_hist.p, c->rs_off.p, kRsBuckets * nb, c->scan_tmp.p, st);
-      hipLaunchKernelGGL(k_rs_scatter, dim3(unsigned(nb)), dim3(256), 0, st, kin, vin, nnz, shift,
-                         c->rs_off.p, nb, kout, vout);
-      std::swap(kin, kout);
-      std::swap(vin, vout);
-      passes++;
-    }
-    // the sorted pairs are in (kin, vin): keep them in (pair_node, nt_rule)
-    if (passes % 2 == 0) {
+    const int64_t hw = radix_hist_words(nnz);
+    if ((rc = c->rs_hist.ensure(hw))) return rc;
+    if ((rc = c->rs_off.ensure(hw + 1))) return rc;
+    if ((rc = c->scan_tmp.ensure(std::max(c->scan_tmp.cap, scan_temp_bytes(hw))))) return rc;
+    bool in_second = false;
+    radix_by_key_enqueue(st, reinterpret_cast<uint32_t*>(c->rn_nodes.p), c->pair_rule.p,
+                         reinterpret_cast<uint32_t*>(c->pair_node.p), c->nt_rule.p, nnz, N, c->rs_hist.p,
+                         c->rs_off.p, c->scan_tmp.p, &in_second);
+    // keep the sorted pairs in (pair_node, nt_rule)
+    if (!in_second) {
       std::swap(c->rn_nodes, c->pair_node);
       std::swap(c->pair_rule, c->nt_rule);
     }
   }
-  hipLaunchKernelGGL(k_node_bounds, dim3(gridn(int64_t(N) + 1, 256, 1 << 30)), dim3(256), 0, st,
-                     reinterpret_cast<const uint32_t*>(c->pair_node.p), nnz, N, c->nt_off.p);
+  launch_node_bounds(st, reinterpret_cast<const uint32_t*>(c->pair_node.p), nnz, N, c->nt_off.p);
   return cg_hip_check(hipGetLastError(), "transpose");
 }
+
+namespace {
 
 // Rules per band: the band's rule-major fire lists (E_band * 8 B) should sit
 // in one XCD's 4 MiB L2 beside the write stream; a power of two, so the

@@ -10,6 +10,9 @@ dispatcher (cg_dispatcher_*, Engine.dispatcher).
   wake(now)                 one timer wake of run() (cron.go:234-244), returns
                             the entries it ran -- the loop body, callable
                             directly for deterministic drivers and tests
+  ClusterCron(jobset)       every cronnode's Cron as one table: begin(now) /
+                            wake(now) -> {node ID: [(Job.ID, Rule.ID), ...]}
+                            (cg_dispatcher_bind_rules + cg_dispatcher_fanout)
 
 Entry state (schedule, Next, Prev) lives in HBM; a wake is one fused kernel
 plus an ordered compaction instead of sort.Sort over every entry.  Jobs run on
@@ -22,7 +25,9 @@ import time
 from dataclasses import dataclass
 from typing import Any, Dict, List, Optional
 
-from ._lib import ZERO_TIME
+import numpy as np
+
+from ._lib import EXCLUDE_NONE, ZERO_TIME
 from .cron import Parse, Schedule as _Schedule
 
 log = logging.getLogger("cronsun_amd.cron")
@@ -199,6 +204,63 @@ class Cron:
             self._thread = None
 
 
+class ClusterCron:
+    """Every cronnode's Cron at once: one dispatcher table over all rules of
+    a model.JobSet (slot i = rule i), fanned out to nodes after each wake.
+    A cronnode runs its own Cron over Job.Cmds(node, groups)
+    (node/node.go:121-158); wake(now) returns what each of those run loops
+    fires at that instant.  No thread: the deterministic driver, like
+    Cron.begin / Cron.wake."""
+
+    def __init__(self, jobset, location=None, mode=EXCLUDE_NONE, engine=None):
+        self.jobset = jobset
+        self._loc = location
+        self._mode = mode
+        self._engine = engine
+        self._d = None
+        self._rules = None
+
+    def begin(self, now):
+        """Upload the set's schedules and rules, start the table at `now`
+        (cron.go:212-215) and bind the rule -> node join."""
+        from .engine import default_engine
+        self._engine = self._engine or default_engine()
+        js = self.jobset
+        self._rules = self._engine.upload_rules(js.rules_in())
+        self._d = self._engine.dispatcher(js.schedules(), self._loc, now)
+        self._d.bind_rules(self._rules, self._mode)
+        self._node_ids = {}
+        self._cmd = [(js.jobs[j].ID, r.ID) for j, r in zip(js.rule_job, js.rules)]
+
+    @property
+    def effective(self):
+        return self._d.effective
+
+    def wake(self, now):
+        """The timer fired at `now`: {node ID: [(Job.ID, Rule.ID), ...]} of the
+        nodes with something due, each node's Cmds in job order, then rule
+        order."""
+        if self._d.effective == ZERO_TIME or now < self._d.effective:
+            return {}
+        self._d.fire_count(now)
+        node_off, slots = self._d.fanout()
+        out = {}
+        for n in np.flatnonzero(np.diff(node_off)):
+            nid = self._node_ids.get(int(n))
+            if nid is None:
+                nid = self._node_ids[int(n)] = self.jobset.node_id(int(n))
+            out[nid] = [self._cmd[int(s)] for s in slots[node_off[n]:node_off[n + 1]]]
+        return out
+
+    def close(self):
+        if self._d is not None:
+            self._d.free()
+            self._d = None
+        if self._rules is not None:
+            self._rules.free()
+            self._rules = None
+
+
 def New():
     """cron.go:82-85 (the local zone: the product needs an explicit Location;
     None means UTC here)."""
@@ -209,4 +271,4 @@ def NewWithLocation(location):
     return Cron(location)
 
 
-__all__ = ["Cron", "Entry", "FuncJob", "New", "NewWithLocation"]
+__all__ = ["ClusterCron", "Cron", "Entry", "FuncJob", "New", "NewWithLocation"]

@@ -170,6 +170,48 @@ class Dispatcher:
         ix = np.ascontiguousarray(np.atleast_1d(idx), dtype=np.int64)
         check(lib().cg_dispatcher_remove(self._h, ix.ctypes.data, len(ix)))
 
+    # ------------------------------------------------------ node fan-out
+    def bind_rules(self, drules, mode=_lib.EXCLUDE_NONE):
+        """Slot i is rule i of the uploaded rule set `drules`: builds the
+        rule -> node join the fan-out of a wake uses (bind again after an edit
+        of groups or rules)."""
+        check(lib().cg_dispatcher_bind_rules(self._h, drules._h, int(mode)))
+        self._n_nodes = drules.n_nodes
+
+    def set_fanout_path(self, path):
+        """CG_FANOUT_AUTO (default) / _FILTER / _DUE: force a device path
+        (instrumentation)."""
+        check(lib().cg_dispatcher_set_fanout_path(self._h, int(path)))
+
+    def fanout_count(self):
+        """Fan the last wake out to nodes, leaving the result in HBM: the
+        number of (node, slot) pairs."""
+        n = C.c_int64()
+        check(lib().cg_dispatcher_fanout(self._h, C.byref(n)))
+        return n.value
+
+    def fanout(self):
+        """The last wake fanned out to nodes: (node_off [N+1], slots) -- node
+        n runs slots[node_off[n]:node_off[n+1]], ascending."""
+        n = self.fanout_count()
+        node_off = np.empty(getattr(self, "_n_nodes", 0) + 1, dtype=np.int64)
+        slots = np.empty(max(n, 1), dtype=np.int32)
+        check(lib().cg_dispatcher_fanout_copy(self._h, node_off.ctypes.data, slots.ctypes.data, n))
+        return node_off, slots[:n]
+
+    def fanout_range(self, first, count):
+        """Pairs [first, first+count) of the last fan-out's slots (one node's
+        list: first = node_off[n])."""
+        out = np.empty(max(int(count), 1), dtype=np.int32)
+        check(lib().cg_dispatcher_fanout_range(self._h, int(first), int(count), out.ctypes.data))
+        return out[:count]
+
+    def fanout_device(self):
+        """(node_off pointer, slots pointer, n_pairs) of the last fan-out in HBM."""
+        off, sl, n = C.c_void_p(), C.c_void_p(), C.c_int64()
+        check(lib().cg_dispatcher_fanout_device(self._h, C.byref(off), C.byref(sl), C.byref(n)))
+        return off.value, sl.value, n.value
+
     def snapshot(self):
         """(next, prev, live) per slot."""
         n = len(self)
@@ -419,6 +461,13 @@ class Engine:
         buf = (C.c_float * 12)()
         lib().cg_last_kernel_times(self._h, buf, 12)
         return list(buf)[9:12]
+
+    def fanout_ms(self):
+        """ms of the last Dispatcher.fanout (cg_last_kernel_times [13]; it
+        spans the read-back of the pair total between the two passes)."""
+        buf = (C.c_float * 14)()
+        check(lib().cg_last_kernel_times(self._h, buf, 14))
+        return float(buf[13])
 
     def sync(self):
         check(lib().cg_sync(self._h))

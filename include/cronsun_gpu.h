@@ -303,8 +303,8 @@ int cg_result_copy_offsets(cg_ctx* ctx, int64_t* host_offsets /* [R+1] */);
  * [4] write (walk), [5] offsets; of the last per-node call: [6] rule->node
  * join, [7] transpose (when the join is rebuilt) + segment records + per-node
  * offsets, [8] per-node write; [12] the last time-order pass; of the last
- * dispatcher wake: [9] scan, [10] due compaction, [11] advance.  n = entries
- * written. */
+ * dispatcher wake: [9] scan, [10] due compaction, [11] advance; [13] the last
+ * cg_dispatcher_fanout.  n = entries written. */
 int cg_last_kernel_times(cg_ctx* ctx, float* ms, int n);
 /* Expansion phase timing: 2 (default) = a HIP event between every phase;
  * 1 = events around k_write_cf only ([3]; [0..2], [4], [5] read -1).  Events
@@ -505,6 +505,58 @@ int cg_expand_per_node_rules_device_async(cg_ctx* ctx, const cg_specs* specs, co
 /* *n_events: the last window's node events (its result is then readable);
  * *n_events_all (may be NULL): the node events of every window waited for. */
 int cg_expand_per_node_wait(cg_ctx* ctx, int64_t* n_events, int64_t* n_events_all);
+
+/* ------------------------------------------- dispatcher node fan-out ---- */
+/* One dispatcher table for a whole cluster: after a wake, which node runs
+ * which of the due entries.  Every cronnode runs its own Cron over its own
+ * Cmds (node/node.go:121-158, node/cron/cron.go:210-275); the fan-out of a
+ * wake is what those N run loops over Job.Cmds(n, groups) fire at that
+ * instant: for every node n ascending, the due slots i (ascending) such that
+ * rule i is scheduled on n under the exclude mode -- the set cg_rule_nodes /
+ * cg_expand_per_node use (Cmd-key last-writer rule, Pause, missing groups).
+ *
+ *   cg_dispatcher_bind_rules  slot i of d is rule i of `rules`: builds the
+ *                             rule->node CSR and its stable node-major
+ *                             transpose into buffers d owns.  CG_EINVAL when
+ *                             the rule set is on another ctx, the mode is
+ *                             bad, d has fewer slots than the set has rules,
+ *                             or pipelined per-node windows / rule-major
+ *                             calls are pending on the ctx.  Binding again
+ *                             rebuilds the join (after an edit of groups or
+ *                             rules).  The ctx's per-node transpose cache is
+ *                             dropped: the next per-node call rebuilds its own.
+ *   cg_dispatcher_fanout      fans out the last cg_dispatcher_fire's due list;
+ *                             *n_pairs = (node, slot) pairs.  The result (and
+ *                             the due list) is valid until the next call on
+ *                             d.  A slot >= n_rules (added by
+ *                             cg_dispatcher_set past the bound set) has no
+ *                             nodes; a replaced slot < n_rules keeps its node
+ *                             set (modCmd changes only the timer,
+ *                             node/node.go:219-238).  CG_EINVAL when d is
+ *                             unbound or no wake was made since the last
+ *                             set / remove.
+ *   cg_dispatcher_fanout_copy node_off [N+1] and the slots to the host
+ *                             (either may be NULL); CG_ECAPACITY naming the
+ *                             required size when cap < n_pairs.
+ *   cg_dispatcher_fanout_range  pairs [first, first+count) of the slots (one
+ *                             node's list: first = node_off[n]).
+ *   cg_dispatcher_fanout_device  the result in HBM.
+ *   cg_dispatcher_set_fanout_path  instrumentation: force the dense (FILTER)
+ *                             or the sparse (DUE) device path; AUTO picks.
+ * cg_last_kernel_times [13] = device time of the last fan-out.
+ * cg_dispatcher_fire and every other call cost what they did: the fan-out
+ * runs only when asked for. */
+#define CG_FANOUT_AUTO 0
+#define CG_FANOUT_FILTER 1 /* stream the transpose, test each rule's due bit */
+#define CG_FANOUT_DUE 2    /* expand the due slots' node lists, sort by node */
+int cg_dispatcher_bind_rules(cg_dispatcher* d, const cg_rules* rules, int mode);
+int cg_dispatcher_fanout(cg_dispatcher* d, int64_t* n_pairs);
+int cg_dispatcher_fanout_copy(const cg_dispatcher* d, int64_t* node_off /* [N+1] */, int32_t* slots,
+                              int64_t cap);
+int cg_dispatcher_fanout_range(const cg_dispatcher* d, int64_t first, int64_t count, int32_t* slots);
+int cg_dispatcher_fanout_device(const cg_dispatcher* d, const int64_t** d_node_off,
+                                const int32_t** d_slots, int64_t* n_pairs);
+int cg_dispatcher_set_fanout_path(cg_dispatcher* d, int path);
 
 /* ------------------------------------------- multi-GPU (RCCL over xGMI) --- */
 /* One process (or thread) per MI355X, each with its own cg_ctx; rules shard

@@ -429,6 +429,7 @@ func (e *Engine) ExpandPerNode(sp *Specs, z *Zone, t0, t1 time.Time, j *Jobset, 
 type Dispatcher struct {
 	d *C.cg_dispatcher
 	e *Engine // cg_dispatcher_free locks the engine's context: keep it reachable
+	nodes int // nodes of the bound jobset (BindRules)
 }
 
 func (e *Engine) NewDispatcher(sp *Specs, z *Zone, now time.Time) (*Dispatcher, error) {
@@ -436,7 +437,7 @@ func (e *Engine) NewDispatcher(sp *Specs, z *Zone, now time.Time) (*Dispatcher, 
 	if rc := C.cg_dispatcher_new(e.ctx, sp.s, z.z, C.int64_t(now.Unix()), &d); rc != 0 {
 		return nil, lastErr(rc)
 	}
-	dd := &Dispatcher{d, e}
+	dd := &Dispatcher{d: d, e: e}
 	runtime.SetFinalizer(dd, func(d *Dispatcher) { C.cg_dispatcher_free(d.d) })
 	runtime.KeepAlive(sp)
 	runtime.KeepAlive(z)
@@ -512,6 +513,94 @@ func (d *Dispatcher) Remove(idx []int64) error {
 		return lastErr(rc)
 	}
 	return nil
+}
+
+// Fan-out paths of SetFanoutPath (instrumentation; Auto picks per wake).
+const (
+	FanoutAuto   = int(C.CG_FANOUT_AUTO)
+	FanoutFilter = int(C.CG_FANOUT_FILTER)
+	FanoutDue    = int(C.CG_FANOUT_DUE)
+)
+
+// BindRules makes slot i of the dispatcher rule i of the jobset: one table for
+// every cronnode's Cron (node/node.go:121-158).  It uploads the jobset's rules
+// and builds the rule -> node join Fanout uses; call it again after an edit of
+// groups or rules.
+func (d *Dispatcher) BindRules(j *Jobset, mode int) error {
+	defer runtime.KeepAlive(d)
+	defer runtime.KeepAlive(j)
+	var rin C.cg_rules_in
+	if rc := C.cg_jobset_rules(j.js, &rin); rc != 0 {
+		return lastErr(rc)
+	}
+	var r *C.cg_rules
+	if rc := C.cg_rules_upload(d.e.ctx, &rin, &r); rc != 0 {
+		return lastErr(rc)
+	}
+	defer C.cg_rules_free(r) // the join is copied into the dispatcher
+	if rc := C.cg_dispatcher_bind_rules(d.d, r, C.int(mode)); rc != 0 {
+		return lastErr(rc)
+	}
+	d.nodes = int(rin.n_nodes)
+	return nil
+}
+
+// SetFanoutPath forces a device path of Fanout (FanoutAuto is the default).
+func (d *Dispatcher) SetFanoutPath(path int) error {
+	rc := C.cg_dispatcher_set_fanout_path(d.d, C.int(path))
+	runtime.KeepAlive(d)
+	if rc != 0 {
+		return lastErr(rc)
+	}
+	return nil
+}
+
+// Fanout fans the last Fire out to nodes: node n runs
+// slots[nodeOff[n]:nodeOff[n+1]] (ascending), what that node's own Cron over
+// Job.Cmds(n, groups) fires at this wake.
+func (d *Dispatcher) Fanout() (nodeOff []int64, slots []int32, err error) {
+	defer runtime.KeepAlive(d)
+	var n C.int64_t
+	if rc := C.cg_dispatcher_fanout(d.d, &n); rc != 0 {
+		return nil, nil, lastErr(rc)
+	}
+	nodeOff = make([]int64, d.nodes+1)
+	slots = make([]int32, n)
+	var sp *C.int32_t
+	if n > 0 {
+		sp = (*C.int32_t)(unsafe.Pointer(&slots[0]))
+	}
+	if rc := C.cg_dispatcher_fanout_copy(d.d, (*C.int64_t)(unsafe.Pointer(&nodeOff[0])), sp, n); rc != 0 {
+		return nil, nil, lastErr(rc)
+	}
+	return nodeOff, slots, nil
+}
+
+// FanoutRange copies pairs [first, first+count) of the last Fanout's slots
+// (one node's list: first = nodeOff[n]).
+func (d *Dispatcher) FanoutRange(first, count int64) ([]int32, error) {
+	defer runtime.KeepAlive(d)
+	out := make([]int32, count)
+	if count == 0 {
+		return out, nil
+	}
+	if rc := C.cg_dispatcher_fanout_range(d.d, C.int64_t(first), C.int64_t(count),
+		(*C.int32_t)(unsafe.Pointer(&out[0]))); rc != 0 {
+		return nil, lastErr(rc)
+	}
+	return out, nil
+}
+
+// FanoutDevice is the last Fanout in HBM (valid until the next call on d).
+func (d *Dispatcher) FanoutDevice() (dNodeOff, dSlots uintptr, nPairs int64, err error) {
+	defer runtime.KeepAlive(d)
+	var off *C.int64_t
+	var sl *C.int32_t
+	var n C.int64_t
+	if rc := C.cg_dispatcher_fanout_device(d.d, &off, &sl, &n); rc != 0 {
+		return 0, 0, 0, lastErr(rc)
+	}
+	return uintptr(unsafe.Pointer(off)), uintptr(unsafe.Pointer(sl)), int64(n), nil
 }
 
 // Comm is the library's RCCL communicator (cg_comm_*): one rank per MI355X of
