@@ -2,6 +2,7 @@
 #pragma once
 #include <hip/hip_runtime.h>
 
+#include <algorithm>
 #include <mutex>
 #include <string>
 #include <vector>
@@ -19,11 +20,6 @@ int cg_hip_check(hipError_t e, const char* what);
     if (_rc != CG_OK) return _rc;    \
   } while (0)
 
-// Grow-only device buffer (grows by 1.25x so repeated calls settle).
-// per-node writer record of one non-empty (node, rule) pair of a segment
-// (cg_pernode.hip, k_seg_records): rule, first position in the segment, and
-// x, st -- fire at position p = t0 + x + p * st (a progression rule), or
-// band-relative fire-list index = x + p when st == 0
 // per rule of a per-node window (k_rule_info): fire count, band-relative
 // index of the first fire, and {first - t0, stride} of a progression (st 0:
 // not one)
@@ -31,10 +27,22 @@ struct alignas(16) RuleInfo {
   int32_t cnt, off, first, st;
 };
 
+// per-node writer record of one non-empty (node, rule) pair of a segment
+// (cg_pernode.hip, k_seg_records): rule, first position in the segment, and
+// x, st -- fire at position p = t0 + x + p * st (a progression rule), or
+// band-relative fire-list index = x + p when st == 0
 struct alignas(16) PairRec {
   int32_t rule, dst, x, st;
 };
 
+// blocks of `threads` items for n items: at least one, at most cap
+inline int gridn(int64_t n, int threads, int cap) {
+  int64_t b = (n + threads - 1) / threads;
+  if (b < 1) b = 1;
+  return int(std::min<int64_t>(b, cap));
+}
+
+// Grow-only device buffer (grows by 1.25x so repeated calls settle).
 template <class T>
 struct DBuf {
   T* p = nullptr;
@@ -122,20 +130,51 @@ struct AsyncSet {
   }
 };
 
+// One per-node window's device chain (cg_pernode.hip): what pn_records_enqueue
+// builds from the window's rule-major fire lists and pn_writer_enqueue reads.
+// The synchronous path has one (cg_ctx::pn), every pipelined set its own.
+struct PnWindow {
+  DBuf<RuleInfo> rule_info;         // per rule (k_rule_info)
+  DBuf<int64_t> seg_cnt, seg_pos;   // per (node, band) segment: events, their scan [N*K+1]
+  DBuf<int32_t> seg_nrec;           // per segment: non-empty pairs
+  DBuf<PairRec> recs;               // their records (k_seg_records)
+  DBuf<uint32_t> tickets;           // the writer's task tickets
+  // the owner's node offsets [N+1] and scan temporary (not owned: the
+  // synchronous path's are the ctx's readable result and shared temporary)
+  int64_t* node_off = nullptr;
+  void* scan_tmp = nullptr;
+  // mapped pinned result words: [0] node events, [1] size error, [2] order check
+  int64_t* res_host = nullptr;
+  int64_t* res_dev = nullptr;
+  // the window pn_records_enqueue was last given (the writer's arguments)
+  const int64_t* offsets = nullptr;
+  const int64_t* times = nullptr;
+  int64_t t0 = 0;
+  int32_t N = 0, K = 0, B = 0;
+  int ensure_res() {
+    if (res_host) return CG_OK;
+    HIPCHK(hipHostMalloc(reinterpret_cast<void**>(&res_host), 32, hipHostMallocMapped | hipHostMallocCoherent));
+    HIPCHK(hipHostGetDevicePointer(reinterpret_cast<void**>(&res_dev), res_host, 0));
+    res_host[0] = res_host[1] = res_host[2] = 0;
+    return CG_OK;
+  }
+  void release() {
+    rule_info.release(); seg_cnt.release(); seg_pos.release(); seg_nrec.release();
+    recs.release(); tickets.release();
+    if (res_host) (void)hipHostFree(res_host);
+    res_host = res_dev = nullptr;
+  }
+};
+
 // One set of the pipelined per-node path (cg_expand_per_node_rules_device_async):
-// the window's rule-major expansion (its own run set and fire times), rule
-// infos and segment records, so window k+1's expansion and records are built
-// on the second stream while window k's per-node writer streams on the first.
+// the window's rule-major expansion (its own run set and fire times) and its
+// chain, so window k+1's expansion and records are built on the second stream
+// while window k's per-node writer streams on the first.
 struct PnAsyncSet {
   AsyncSet rm;
-  DBuf<int64_t> times, seg_cnt, seg_pos, node_off;
-  DBuf<int32_t> seg_nrec;
-  DBuf<RuleInfo> rule_info;
-  DBuf<PairRec> recs;
-  DBuf<uint32_t> tickets;
+  PnWindow w;
+  DBuf<int64_t> times, node_off;
   DBuf<char> seg_tmp;
-  int64_t* res_host = nullptr;  // {En, error}: mapped pinned, written by the records / node offsets
-  int64_t* res_dev = nullptr;
   hipEvent_t side_done = nullptr, written = nullptr, nw0 = nullptr, nw1 = nullptr;
   bool pending = false;
   bool timed = false;  // the window's lists are written in (time, rule) order
@@ -143,10 +182,8 @@ struct PnAsyncSet {
   int32_t N = 0;
   void release() {
     rm.release();
-    times.release(); seg_cnt.release(); seg_pos.release(); node_off.release(); seg_nrec.release();
-    rule_info.release(); recs.release(); tickets.release(); seg_tmp.release();
-    if (res_host) (void)hipHostFree(res_host);
-    res_host = res_dev = nullptr;
+    w.release();
+    times.release(); node_off.release(); seg_tmp.release();
     for (hipEvent_t* e : {&side_done, &written, &nw0, &nw1})
       if (*e) (void)hipEventDestroy(*e), *e = nullptr;
   }
@@ -222,13 +259,11 @@ struct cg_ctx {
   int64_t pa_en_sum = 0;  // node events of the checked calls since the last wait
 
   // per-node buffers: the rule->node join (rule-major pairs), its node-major
-  // transpose, the (node, rule band) segments and the node CSR
-  DBuf<int64_t> rn_off, node_off, node_time, nt_off, rs_off, seg_pair, seg_cnt, seg_pos;
+  // transpose, the (node, rule band) segment bounds, the node CSR and the
+  // synchronous path's window chain
+  DBuf<int64_t> rn_off, node_off, node_time, nt_off, rs_off, seg_pair;
   DBuf<int32_t> rn_cnt, rn_nodes, pair_node, pair_rule, node_rule, nt_rule, rs_hist;
-  DBuf<int32_t> seg_nrec;
-  DBuf<PairRec> recs;  // per-call segment records (k_seg_records)
-  DBuf<RuleInfo> rule_info;  // per-call, per rule (k_rule_info)
-  DBuf<uint32_t> pn_tickets;
+  PnWindow pn;
   // time-order pass (cg_node_order.hip): node-aligned tiles, per-pass
   // histograms/offsets, and the second buffers of the ping-pong
   DBuf<int32_t> ts_cnt, ts_tile_node, ts_hist, node_rule2;
@@ -247,8 +282,6 @@ struct cg_ctx {
   // prefix over runs, and a scratch copy of one node group
   DBuf<int64_t> mr_rb, mr_tp, mr_t;
   DBuf<int32_t> mr_r;
-  int64_t* pn_res_host = nullptr;  // mapped pinned: per-node event total of the last call
-  int64_t* pn_res_dev = nullptr;
   // the rule->node join + transpose depend only on (rule set, exclude mode):
   // kept across per-node calls on the same uploaded rule set (time windows);
   // the segment bounds also on the band width
@@ -282,18 +315,13 @@ struct cg_ctx {
     res_dev = nullptr;
     run_dmask.release(); scan_tmp.release(); stuck.release(); cksum.release();
     rn_off.release(); node_off.release(); node_time.release(); nt_off.release(); rs_off.release();
-    seg_pair.release(); seg_cnt.release(); seg_pos.release(); rn_cnt.release(); rn_nodes.release();
+    seg_pair.release(); rn_cnt.release(); rn_nodes.release();
     pair_node.release(); pair_rule.release(); node_rule.release(); nt_rule.release();
-    rs_hist.release(); pn_tickets.release(); rules.release();
-    seg_nrec.release(); recs.release();
-    rule_info.release();
+    rs_hist.release(); pn.release(); rules.release();
     ts_cnt.release(); ts_tile_node.release(); ts_hist.release(); node_rule2.release();
     ts_start.release(); ts_hi.release();
     ts_base.release(); ts_off.release(); node_time2.release(); ts_node_off.release();
     mr_rb.release(); mr_tp.release(); mr_t.release(); mr_r.release();
-    if (pn_res_host) (void)hipHostFree(pn_res_host);
-    pn_res_host = nullptr;
-    pn_res_dev = nullptr;
   }
 };
 
@@ -344,6 +372,8 @@ bool pn_async_pending(const cg_ctx* c);  // an asynchronous expansion not yet wa
 // stable node-major transpose (nt_off [N+1], nt_rule [nnz]; rn_nodes /
 // pair_rule are consumed); c->mu held.  The per-node path caches these buffers
 // by (pn_cache_serial, pn_cache_mode): any other caller clears pn_cache_serial.
+// (cg_rule_nodes.hip; upload_rules validates a host rule set and copies it into a device store)
+int upload_rules(const cg_rules_in* in, RulesStore* st, hipStream_t s);
 int rule_nodes_locked(cg_ctx* c, const RulesStore& st, int mode, int64_t* nnz_out);
 int transpose_locked(cg_ctx* c, int64_t nnz, int32_t N);
 // The transpose's stable LSD passes (k_rs_hist / k_rs_scatter, 8 bits a pass)
@@ -360,8 +390,8 @@ void launch_node_bounds(hipStream_t st, const uint32_t* keys, int64_t n, int32_t
 // cg_node_order.hip), enqueued on st without a host sync
 // in_mode: what the writer left in c->node_time / c->node_rule -- kInTimes
 // int64 times + rules; kIn16 16-bit offsets t - t0 - 1 + rules
-// (k_node_write<.., kOut16>); kInPacked one word per event, offset << 20 |
-// (rule & 0xFFFFF), in c->node_rule (k_node_write<.., kOutPacked>; rules <
+// (k_node_write<.., kIn16>); kInPacked one word per event, offset << 20 |
+// (rule & 0xFFFFF), in c->node_rule (k_node_write<.., kInPacked>; rules <
 // 2^24: past 2^20 the tiles are cut where rule >> 20 changes and carry it)
 constexpr int kInTimes = 0, kIn16 = 1, kInPacked = 2;
 // the time-order writer may emit kInPacked for R rules (indices < 2^24)
@@ -381,11 +411,9 @@ int order_merge_enqueue(cg_ctx* c, const int64_t* node_off, int32_t N, int64_t c
                         hipStream_t st, int in_mode, int64_t* err, const TileCut& cut = TileCut());
 constexpr const char* kOrderCheckMsg =
     "time-order pass: a sorted chunk came out of (time, rule) order (its LDS-atomic ranks were not in lane order)";
-// the mapped pinned per-node result words: [0] node events, [1] size error, [2] order check
-int pn_ensure_res(cg_ctx* c);
 // the time-order pass over the last (rule-major) per-node result; c->mu held
 int order_by_time_locked(cg_ctx* c, int in_mode = 0);
-// kernels of the per-node CSR gather (cg_pernode.hip), enqueued on st:
+// kernels of the per-node CSR gather (cg_node_gather.hip), enqueued on st:
 // node n's events [src_off[n], src_off[n+1]) of src to dst_start[n] onwards /
 // n contiguous events / the last per-node result's counts per node
 // (event i of src_off's numbering at src_*[i - src_shift])

@@ -1171,9 +1171,6 @@ __global__ __launch_bounds__(256) void k_ot_big(const uint16_t* __restrict__ tin
   }
 }
 
-int gridn(int64_t n, int threads) { return int(std::max<int64_t>(1, (n + threads - 1) / threads)); }
-
-
 }  // namespace
 
 // Windows <= 4096 s, in three steps enqueued on st with no host sync (buffers
@@ -1201,9 +1198,9 @@ int order_setup(cg_ctx* c, const int64_t* node_off, int32_t N, int64_t cap, hipS
       (rc = c->node_rule2.ensure(cap)) || (rc = c->ts_off.ensure(tab)) || (rc = c->ts_start.ensure(*Tmax + 1)) ||
       (rc = c->ts_hi.ensure(*Tmax)) || (rc = c->scan_tmp.ensure(std::max(c->scan_tmp.cap, scan_temp_bytes(N)))))
     return rc;
-  hipLaunchKernelGGL(k_ot_tile_count, dim3(gridn(N, 256)), dim3(256), 0, st, node_off, N, cap, cut, c->ts_cnt.p);
+  hipLaunchKernelGGL(k_ot_tile_count, dim3(gridn(N, 256, 1 << 30)), dim3(256), 0, st, node_off, N, cap, cut, c->ts_cnt.p);
   launch_scan(c->ts_cnt.p, c->ts_base.p, N, c->scan_tmp.p, st);
-  hipLaunchKernelGGL(k_ot_tiles, dim3(gridn(N, 256)), dim3(256), 0, st, c->ts_base.p, node_off, N, cut,
+  hipLaunchKernelGGL(k_ot_tiles, dim3(gridn(N, 256, 1 << 30)), dim3(256), 0, st, c->ts_base.p, node_off, N, cut,
                      c->ts_tile_node.p, c->ts_start.p, c->ts_hi.p);
   return cg_hip_check(hipGetLastError(), "time-order tiles");
 }
@@ -1396,23 +1393,23 @@ int order_by_time_locked(cg_ctx* c, int in_mode) {
 
   // windows <= 4096 s: tile sort + merge (CG_ORDER_LSD=1: the LSD passes)
   if (bits <= 12 && !order_lsd_only()) {
-    if ((rc = pn_ensure_res(c))) return rc;
-    c->pn_res_host[2] = 0;
+    if ((rc = c->pn.ensure_res())) return rc;
+    c->pn.res_host[2] = 0;
     (void)hipEventRecord(c->pev[0], st);
     TileCut cut;  // the writer's packed words past 2^20 rules: tiles cut at the band offsets of this result
-    if (in_mode == kInPacked) cut = TileCut{c->seg_pos.p, c->pn_K, c->pn_B, c->pn_R};
-    if ((rc = order_merge_enqueue(c, c->node_off.p, N, En, c->pn_t0, H, st, in_mode, c->pn_res_dev + 2, cut)))
+    if (in_mode == kInPacked) cut = TileCut{c->pn.seg_pos.p, c->pn_K, c->pn_B, c->pn_R};
+    if ((rc = order_merge_enqueue(c, c->node_off.p, N, En, c->pn_t0, H, st, in_mode, c->pn.res_dev + 2, cut)))
       return rc;
     (void)hipEventRecord(c->pev[1], st);
     if ((rc = cg_hip_check(hipStreamSynchronize(st), "sync"))) return rc;
-    if (c->pn_res_host[2]) return cg_fail(CG_EHIP, kOrderCheckMsg);
+    if (c->pn.res_host[2]) return cg_fail(CG_EHIP, kOrderCheckMsg);
     (void)hipEventElapsedTime(&c->kt[12], c->pev[0], c->pev[1]);
     c->pn_time_ordered = true;
     return CG_OK;
   }
   if ((rc = c->ts_cnt.ensure(N)) || (rc = c->ts_base.ensure(int64_t(N) + 1))) return rc;
   if ((rc = c->scan_tmp.ensure(std::max(c->scan_tmp.cap, scan_temp_bytes(N))))) return rc;
-  hipLaunchKernelGGL(k_ts_tile_count, dim3(gridn(N, 256)), dim3(256), 0, st, c->node_off.p, N, kTsTile, En,
+  hipLaunchKernelGGL(k_ts_tile_count, dim3(gridn(N, 256, 1 << 30)), dim3(256), 0, st, c->node_off.p, N, kTsTile, En,
                      c->ts_cnt.p);
   launch_scan(c->ts_cnt.p, c->ts_base.p, N, c->scan_tmp.p, st);
   int64_t T = 0;
@@ -1423,7 +1420,7 @@ int order_by_time_locked(cg_ctx* c, int in_mode) {
       (rc = c->ts_off.ensure(T * kTsDigits)) || (rc = c->node_time2.ensure(En)) || (rc = c->node_rule2.ensure(En)))
     return rc;
   (void)hipEventRecord(c->pev[0], st);
-  hipLaunchKernelGGL(k_ts_tiles, dim3(gridn(N, 256)), dim3(256), 0, st, c->ts_base.p, N, c->ts_tile_node.p);
+  hipLaunchKernelGGL(k_ts_tiles, dim3(gridn(N, 256, 1 << 30)), dim3(256), 0, st, c->ts_base.p, N, c->ts_tile_node.p);
   int64_t* tin = c->node_time.p;
   int32_t* rin = c->node_rule.p;
   int64_t* tout = c->node_time2.p;
