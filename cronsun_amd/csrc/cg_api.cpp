@@ -128,6 +128,7 @@ int cg_init(int device, cg_ctx** out) {
   if (const char* e = getenv("CG_WRITE_BLOCKS_PER_CU")) per_cu = std::max(1, atoi(e));
 #endif
   c->write_blocks = std::max(1, prop.multiProcessorCount) * per_cu;
+  c->write_blocks_ov = std::max(1, prop.multiProcessorCount) * std::min(per_cu, kWriteBlocksPerCUOverlap);
   if (hipStreamCreateWithFlags(&c->st, hipStreamNonBlocking) != hipSuccess) {
     delete c;
     return cg_fail(CG_EHIP, "hipStreamCreate failed");
@@ -146,6 +147,7 @@ void cg_destroy(cg_ctx* c) {
   (void)hipSetDevice(c->device);
   (void)hipStreamSynchronize(c->st);
   if (c->st_cs) (void)hipStreamSynchronize(c->st_cs);
+  if (c->st_w1) (void)hipStreamSynchronize(c->st_w1);
   c->free_all();
   for (auto& e : c->ev) (void)hipEventDestroy(e);
   for (auto& e : c->pev) (void)hipEventDestroy(e);
@@ -157,6 +159,7 @@ int cg_sync(cg_ctx* c) {
   if (!c) return cg_fail(CG_EINVAL, "cg_sync: null");
   HIPCHK(hipSetDevice(c->device));
   HIPCHK(hipStreamSynchronize(c->st));
+  if (c->st_w1) HIPCHK(hipStreamSynchronize(c->st_w1));  // the pipelined path's second writer stream
   return CG_OK;
 }
 
@@ -428,6 +431,7 @@ static int count_phase(cg_ctx* c, const cg_specs* s, const cg_zone* z, int64_t t
   c->pa_last = -1;
   c->pa_en_sum = 0;
   c->as_last = -1;
+  c->times_last = 0;  // synchronous calls write c->times
   c->last_R = 0;
   c->last_E = 0;
   HIPCHK(hipSetDevice(c->device));
@@ -633,7 +637,7 @@ int cg_result_device(cg_ctx* c, const int64_t** d_off, const int64_t** d_times, 
   std::lock_guard<std::mutex> g(c->mu);
   if (int rc = refuse_pending(c, "cg_result_device")) return rc;
   if (d_off) *d_off = c->as_last >= 0 ? c->as[c->as_last].offsets.p : c->offsets.p;
-  if (d_times) *d_times = c->times.p;
+  if (d_times) *d_times = c->result_times();
   if (n) *n = c->last_E;
   return CG_OK;
 }
@@ -646,7 +650,7 @@ int cg_result_copy_times(cg_ctx* c, int64_t first, int64_t count, int64_t* host)
     return cg_fail(CG_EINVAL, "range outside the last result");
   (void)hipGetLastError();  // clear a stale error so launch checks see only their own
   HIPCHK(hipSetDevice(c->device));
-  if (count) HIPCHK(hipMemcpy(host, c->times.p + first, count * 8, hipMemcpyDeviceToHost));
+  if (count) HIPCHK(hipMemcpy(host, c->result_times() + first, count * 8, hipMemcpyDeviceToHost));
   return CG_OK;
 }
 

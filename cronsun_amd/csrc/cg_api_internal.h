@@ -112,8 +112,12 @@ struct AsyncSet {
   bool plan_valid = false;
   uint64_t plan_zone = 0;
   int64_t plan_t0 = 0, plan_t1 = 0;
-  hipEvent_t written = nullptr, w0 = nullptr, w1 = nullptr;  // writer done; writer start/end
-  bool written_w1 = false;  // the set's writer-done event is w1 (no walk kernel)
+  hipEvent_t written = nullptr;  // recorded behind the walk writer
+  // the set's writer-done event of its last call: `written`, or without a walk
+  // kernel the call's end-of-writer timing event (not owned; null: none yet)
+  hipEvent_t done = nullptr;
+  int tslot = 0;   // the call's pair in the ctx's timing-event ring
+  int tprev = -1;  // the previous call's pair when its writer may overlap this one's (-1: none)
   bool pending = false;  // a call on this set whose record has not been checked
   bool armed = false;    // stuck flag holds ~0 (set once; every scan re-arms it)
   int64_t R = 0, cap = 0;
@@ -125,8 +129,8 @@ struct AsyncSet {
     res_host = res_dev = nullptr;
     plan_pin = nullptr;
     plan_pin_cap = 0;
-    for (hipEvent_t* e : {&written, &w0, &w1})
-      if (*e) (void)hipEventDestroy(*e), *e = nullptr;
+    if (written) (void)hipEventDestroy(written), written = nullptr;
+    done = nullptr;
   }
 };
 
@@ -192,6 +196,7 @@ struct PnAsyncSet {
 struct cg_ctx {
   int device = 0;
   int write_blocks = 1024;  // persistent k_write_cf grid (set from the CU count)
+  int write_blocks_ov = 1024;  // of each of two overlapped pipelined writers (kWriteBlocksPerCUOverlap)
   hipStream_t st = nullptr;
   hipEvent_t ev[8] = {};
   hipEvent_t pev[4] = {};  // per-node phases
@@ -238,7 +243,10 @@ struct cg_ctx {
   // run in the previous writer's tail instead of racing the next writer's
   // start (two sets: the count alternately ran before and after that start,
   // 19 vs 50 us between writers, profiles/r02_ab_async_sets.json)
-  static constexpr int kAsyncSets = 3;
+#ifndef CG_ASYNC_SETS
+#define CG_ASYNC_SETS 3
+#endif
+  static constexpr int kAsyncSets = CG_ASYNC_SETS;
   AsyncSet as[kAsyncSets];
   int as_next = 0, as_last = -1;
   hipStream_t st_cs = nullptr;
@@ -247,6 +255,27 @@ struct cg_ctx {
   std::string async_msg;
   double wr_ms_sum = 0;  // writer (k_write_cf) time of the checked async calls
   int wr_n = 0;
+  // Writer overlap: pipelined call k runs its writer on writer stream k & 1
+  // (st, st_w1) into output buffer k & 1 (times, times2), so two writers are
+  // resident side by side and the stores never pause between calls
+  // (pipelined steps).  Writers k and k+2
+  // share a stream and a buffer (stream order); neighbours share nothing they
+  // write.  times2 holds at least times.cap events while the overlap is
+  // active; without it every call uses st and times.
+  hipStream_t st_w1 = nullptr;
+  DBuf<int64_t> times2;
+  bool ov_on = true;       // cg_set_async_overlap
+  bool ov_active = false;  // decided by a pipelined call made with nothing pending
+  bool w1_dirty = false;   // work enqueued on st_w1 since it was last synchronised
+  unsigned wr_call = 0;    // pipelined calls so far: its parity picks stream and buffer
+  int times_last = 0;      // the output buffer of the last result (0: times, 1: times2)
+  // writer start / end events of the pipelined calls: a ring one deeper than
+  // the run sets, so the previous call's end is still there when a call is
+  // checked (cg_async.cpp, check_set)
+  static constexpr int kTimeRing = kAsyncSets + 1;
+  hipEvent_t tw0[kTimeRing] = {}, tw1[kTimeRing] = {};
+  int tw_next = 0, tw_prev = -1;  // next pair; the previous call's since the last drain (-1: none)
+  int64_t* result_times() const { return times_last ? times2.p : times.p; }
 
   // pipelined per-node windows (cg_pernode.hip): three sets in turn
   static constexpr int kPnSets = 3;
@@ -300,8 +329,14 @@ struct cg_ctx {
     for (PnAsyncSet& a : pns) a.release();
     for (hipEvent_t& e : cs_done)
       if (e) (void)hipEventDestroy(e), e = nullptr;
+    for (hipEvent_t* ring : {tw0, tw1})
+      for (int i = 0; i < kTimeRing; i++)
+        if (ring[i]) (void)hipEventDestroy(ring[i]), ring[i] = nullptr;
     if (st_cs) (void)hipStreamDestroy(st_cs);
     st_cs = nullptr;
+    if (st_w1) (void)hipStreamDestroy(st_w1);
+    st_w1 = nullptr;
+    times2.release();
     if (ot_fork) (void)hipEventDestroy(ot_fork), ot_fork = nullptr;
     if (ot_join) (void)hipEventDestroy(ot_join), ot_join = nullptr;
     if (st_ot) (void)hipStreamDestroy(st_ot);

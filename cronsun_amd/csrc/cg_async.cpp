@@ -5,10 +5,16 @@
 // caller reads the event total) and runs count -> scan -> write in series.
 // cg_expand_device_async enqueues the same kernels and returns: the count and
 // scan of call k run on a second stream, into a run set no queued writer
-// reads (three sets), while call k-1's writer streams its output; call k's writer then
-// follows call k-1's on the ctx stream.  The plan of each call (zone table,
-// segments, day table) is staged through pinned memory of its run set, so a
-// moving T0 costs no stream sync either.  cg_expand_wait drains the pipeline
+// reads (three sets), while call k-1's writer streams its output.  Call k's
+// writer runs on writer stream k & 1 into output buffer k & 1 (the ctx stream
+// and c->times, a second stream and c->times2): it follows call k-2's in
+// stream order and shares nothing it writes with call k-1's, so the two are
+// resident side by side (kWriteBlocksPerCUOverlap blocks per CU each) and the
+// stores do not pause while one writer ends and the next starts.  Nothing on
+// the device waits for another kernel.  Where the second buffer does not fit (or
+// cg_set_async_overlap(0)) every writer runs on the ctx stream into c->times.
+// The plan of each call (zone table, segments, day table) is staged through
+// pinned memory of its run set, so a moving T0 costs no stream sync either.  cg_expand_wait drains the pipeline
 // and reports the calls' errors: a rule whose reference Next loop never ends
 // (CG_ERANGE), or a result larger than the output capacity sized by an
 // earlier synchronous call (CG_ECAPACITY: the writer then wrote nothing).
@@ -25,18 +31,26 @@
 
 using namespace cg;
 
-#ifndef CG_ASYNC_ONE_EVENT
-#define CG_ASYNC_ONE_EVENT 1
-#endif
-
 namespace {
 
 // the record of a finished call on set a: fold its errors and writer time in
 void check_set(cg_ctx* c, AsyncSet& a) {
   if (!a.pending) return;
   a.pending = false;
+  // the call's writer time: start to end, or with the previous call's writer
+  // on the other stream the part after that writer's end (the time to this
+  // writer's completion not already counted for the previous call)
   float ms = 0.f;
-  if (hipEventElapsedTime(&ms, a.w0, a.w1) == hipSuccess) {
+  if (hipEventElapsedTime(&ms, c->tw0[a.tslot], c->tw1[a.tslot]) == hipSuccess) {
+    if (a.tprev >= 0) {
+      float since_prev = 0.f;
+      const hipError_t e = hipEventElapsedTime(&since_prev, c->tw1[a.tprev], c->tw1[a.tslot]);
+      if (e == hipSuccess)
+        ms = std::min(ms, std::max(since_prev, 0.f));
+      else if (e == hipErrorNotReady)
+        ms = 0.f;  // the previous writer is still running: it ends after this one
+      (void)hipGetLastError();
+    }
     c->wr_ms_sum += ms;
     c->wr_n++;
   }
@@ -63,13 +77,48 @@ int ensure_async(cg_ctx* c) {
   for (hipEvent_t& e : c->cs_done) HIPCHK(hipEventCreateWithFlags(&e, hipEventDisableTiming));
   for (AsyncSet& a : c->as) {
     HIPCHK(hipEventCreateWithFlags(&a.written, hipEventDisableTiming));
-    HIPCHK(hipEventCreateWithFlags(&a.w0, hipEventDisableSystemFence));
-    HIPCHK(hipEventCreateWithFlags(&a.w1, hipEventDisableSystemFence));
     HIPCHK(hipHostMalloc(reinterpret_cast<void**>(&a.res_host), 16, hipHostMallocMapped | hipHostMallocCoherent));
     HIPCHK(hipHostGetDevicePointer(reinterpret_cast<void**>(&a.res_dev), a.res_host, 0));
     a.res_host[0] = 0;
     a.res_host[1] = -1;
   }
+  for (hipEvent_t* ring : {c->tw0, c->tw1})
+    for (int i = 0; i < cg_ctx::kTimeRing; i++) HIPCHK(hipEventCreateWithFlags(&ring[i], hipEventDisableSystemFence));
+  return CG_OK;
+}
+
+// A pipelined call made with nothing pending (both writer streams idle):
+// whether the following calls alternate between two writer streams and output
+// buffers.  The second buffer is taken only when cap events of it are at most
+// half of the device memory free at this moment; where it does not fit, or its
+// allocation fails, the calls run on the ctx stream into c->times alone.
+static int overlap_decide(cg_ctx* c, int64_t cap) {
+  c->ov_active = false;
+  c->tw_prev = -1;
+  if (c->st_w1 && c->w1_dirty) HIPCHK(hipStreamSynchronize(c->st_w1));
+  c->w1_dirty = false;
+  if (!c->ov_on) {
+    c->times2.release();  // the caller's memory back
+    return CG_OK;
+  }
+  if (!c->st_w1 && hipStreamCreateWithFlags(&c->st_w1, hipStreamNonBlocking) != hipSuccess) {
+    c->st_w1 = nullptr;
+    (void)hipGetLastError();
+    return CG_OK;
+  }
+  if (int64_t(c->times2.cap) < cap) {  // a synchronous call grew c->times: follow it
+    c->times2.release();
+    size_t free_b = 0, total_b = 0;
+    int64_t* p = nullptr;
+    if (hipMemGetInfo(&free_b, &total_b) != hipSuccess || size_t(cap) * 8 > free_b / 2 ||
+        hipMalloc(&p, size_t(cap) * 8) != hipSuccess) {
+      (void)hipGetLastError();
+      return CG_OK;
+    }
+    c->times2.p = p;
+    c->times2.cap = size_t(cap);
+  }
+  c->ov_active = true;
   return CG_OK;
 }
 
@@ -83,9 +132,12 @@ bool async_pending(const cg_ctx* c) {
 int async_drain(cg_ctx* c) {
   bool any = false;
   for (const AsyncSet& a : c->as) any = any || a.pending;
-  if (!any) return CG_OK;
+  if (!any && !c->w1_dirty) return CG_OK;
   HIPCHK(hipStreamSynchronize(c->st));
+  if (c->st_w1) HIPCHK(hipStreamSynchronize(c->st_w1));
+  c->w1_dirty = false;
   for (AsyncSet& a : c->as) check_set(c, a);
+  c->tw_prev = -1;  // the next call's writer starts on idle streams
   return CG_OK;
 }
 
@@ -156,17 +208,26 @@ int cg_expand_device_async(cg_ctx* c, const cg_specs* s, const cg_zone* z, int64
     return cg_fail(CG_ECAPACITY, "cg_expand_device_async: no output capacity yet (run cg_expand_device once)");
   int rc = ensure_async(c);
   if (rc) return rc;
+  if (!async_pending(c) && (rc = overlap_decide(c, cap))) return rc;
+  // this call's writer stream and output buffer
+  const int wi = c->ov_active ? int(c->wr_call & 1) : 0;
+  hipStream_t sw = wi ? c->st_w1 : c->st;
+  int64_t* const out = wi ? c->times2.p : c->times.p;
   const int k = c->as_next;
   AsyncSet& a = c->as[k];
   // the set was last used kAsyncSets calls ago: its writer must be done
   // before the host restages its plan or the count stream rewrites its runs
-  HIPCHK(hipEventSynchronize(a.written_w1 ? a.w1 : a.written));
+  if (a.done) HIPCHK(hipEventSynchronize(a.done));
   check_set(c, a);
+  a.done = nullptr;
+  c->wr_call++;
+  c->times_last = wi;
+  if (wi) c->w1_dirty = true;
   const int64_t R = int64_t(s->n);
   bool empty = false;
   if ((rc = async_count_scan(c, a, s, z, t0, t1, cap, &empty))) return rc;
   if (empty) {  // nothing to count: zero offsets, an empty result
-    HIPCHK(hipMemsetAsync(a.offsets.p, 0, (R + 1) * 8, c->st));
+    HIPCHK(hipMemsetAsync(a.offsets.p, 0, (R + 1) * 8, sw));
     a.res_host[0] = 0;
     a.res_host[1] = -1;
     a.R = R;
@@ -179,20 +240,31 @@ int cg_expand_device_async(cg_ctx* c, const cg_specs* s, const cg_zone* z, int64
   const PlanArgs& pa = a.pa;
   const int64_t nruns = R * int64_t(pa.G);
   HIPCHK(hipEventRecord(c->cs_done[k], c->st_cs));
-  // the writer after the previous call's writer, once this call's scan is done
-  HIPCHK(hipStreamWaitEvent(c->st, c->cs_done[k], 0));
+  // the writer after the last one on its stream, once this call's scan is done
+  HIPCHK(hipStreamWaitEvent(sw, c->cs_done[k], 0));
   const bool has_walk = (a.plan.flags & (kPlanT0Walk | kPlanWalkSegs)) != 0;
-  (void)hipEventRecord(a.w0, c->st);
+  // with a writer of this batch possibly still running on the other stream the
+  // two share the CUs: the smaller grid (the first writer after a drain runs
+  // alone at its start and keeps the full one)
+  const int blocks = c->ov_active && c->tw_prev >= 0 ? c->write_blocks_ov : c->write_blocks;
+  a.tslot = c->tw_next;
+  a.tprev = c->ov_active ? c->tw_prev : -1;
+  c->tw_prev = a.tslot;
+  c->tw_next = (a.tslot + 1) % cg_ctx::kTimeRing;
+  (void)hipEventRecord(c->tw0[a.tslot], sw);
   launch_write_cf(s->d, pa, a.run_anchor.p, a.run_count.p, a.run_dmask.p, a.run_off.p, nruns, a.block_run.p, cap,
-                  c->times.p, c->write_blocks, c->st);
-  (void)hipEventRecord(a.w1, c->st);
+                  out, blocks, sw);
+  (void)hipEventRecord(c->tw1[a.tslot], sw);
   if (has_walk)
-    launch_write_walk(s->d, R, pa, a.run_anchor.p, a.run_count.p, a.run_dmask.p, a.run_off.p, cap, c->times.p,
-                      c->st);
-  // the set is free again once its writer is done: without a walk that is w1
-  // (one event packet fewer between back-to-back writers)
-  a.written_w1 = CG_ASYNC_ONE_EVENT && !has_walk;
-  if (!a.written_w1) HIPCHK(hipEventRecord(a.written, c->st));
+    launch_write_walk(s->d, R, pa, a.run_anchor.p, a.run_count.p, a.run_dmask.p, a.run_off.p, cap, out, sw);
+  // the set is free again once its writer is done: without a walk that is the
+  // end-of-writer event (one event packet fewer behind the writer; its ring
+  // pair is re-recorded only after the set's next use has waited for it)
+  a.done = c->tw1[a.tslot];
+  if (has_walk) {
+    HIPCHK(hipEventRecord(a.written, sw));
+    a.done = a.written;
+  }
   HIPCHK(hipGetLastError());
   a.R = R;
   a.cap = cap;
@@ -212,7 +284,7 @@ int cg_expand_wait(cg_ctx* c, int64_t* n_events) {
   int rc = async_drain(c);
   if (rc) return rc;
   if (c->wr_n > 0) {
-    c->kt[3] = float(c->wr_ms_sum / c->wr_n);  // mean writer time of the calls checked
+    c->kt[3] = float(c->wr_ms_sum / c->wr_n);  // mean writer time of the calls checked (check_set)
     for (int i : {0, 1, 2, 4, 5}) c->kt[i] = -1.f;
   }
   c->wr_ms_sum = 0;
@@ -229,6 +301,15 @@ int cg_expand_wait(cg_ctx* c, int64_t* n_events) {
   }
   if (n_events) *n_events = E;  // 0 when no asynchronous call was made since the last synchronous one
   if (rc_async) return cg_fail(rc_async, msg);
+  return CG_OK;
+}
+
+int cg_set_async_overlap(cg_ctx* c, int on) {
+  if (!c) return cg_fail(CG_EINVAL, "cg_set_async_overlap: null");
+  std::lock_guard<std::mutex> g(c->mu);
+  if (async_pending(c))
+    return cg_fail(CG_EINVAL, "cg_set_async_overlap: asynchronous expansions pending (call cg_expand_wait first)");
+  c->ov_on = on != 0;
   return CG_OK;
 }
 

@@ -43,6 +43,17 @@ constexpr int kWriteWaves = CG_WRITE_WAVES;
 #define CG_WRITE_BPC (12 / CG_WRITE_WAVES)
 #endif
 constexpr int kWriteBlocksPerCU = CG_WRITE_BPC;  // persistent grid: blocks of 4 waves per CU
+// Two pipelined writers in flight on two streams (cg_async.cpp) are both
+// resident: 4 blocks per CU each (16 writer waves per CU).  Same-box A/B on
+// config 2, 4 run sets (profiles/r07_ab_overlap_blocks.txt): step 0.897-0.901
+// ms at 4 vs 0.904-0.913 at 6, 0.944-0.975 at 5, 0.953-0.958 at 3 (one writer
+// at a time: 0.980-0.983).  At 6 the 24 writer waves leave k_count 8 wave
+// slots per CU: it takes 790 us instead of 160-240 and every writer waits for
+// its count; at 4 the count takes 244 us and the writers run back to back.
+#ifndef CG_WRITE_BPC_OVERLAP
+#define CG_WRITE_BPC_OVERLAP 4
+#endif
+constexpr int kWriteBlocksPerCUOverlap = CG_WRITE_BPC_OVERLAP;
 // writer slice tickets: one u32 counter per group of blocks, 128 B apart
 #ifndef CG_TICKET_GROUPS
 #define CG_TICKET_GROUPS 32

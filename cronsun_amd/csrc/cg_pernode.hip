@@ -891,6 +891,7 @@ int cg_expand_per_node_rules_device_async(cg_ctx* c, const cg_specs* s, const cg
   if (rc) return rc;
   // the rule-major result and the time-order records no longer describe a result
   c->as_last = -1;
+  c->times_last = 0;
   c->last_R = 0;
   c->last_E = 0;
   const int k = c->pa_next;

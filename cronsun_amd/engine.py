@@ -427,6 +427,12 @@ class Engine:
         check(lib().cg_expand_wait(self._h, C.byref(n)))
         return n.value
 
+    def set_async_overlap(self, on):
+        """Pipelined expansions alternate between two writer streams and output
+        buffers (default, when the second buffer fits) or use one
+        (cg_set_async_overlap); refused while calls are pending."""
+        check(lib().cg_set_async_overlap(self._h, 1 if on else 0))
+
     def result_device(self):
         off, times, n = C.c_void_p(), C.c_void_p(), C.c_int64()
         check(lib().cg_result_device(self._h, C.byref(off), C.byref(times), C.byref(n)))

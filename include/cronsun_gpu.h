@@ -278,10 +278,26 @@ int cg_expand_device(cg_ctx* ctx, const cg_specs* specs, const cg_zone* z, int64
  * call issued since the last wait, returns the first error among them (a
  * rule whose reference loop never ends: CG_ERANGE, as cg_expand_device), and
  * sets *n_events of the last call, whose result the accessors below then
- * read.  cg_last_kernel_times [3] = the mean write time of those calls.
- * Every call writes into the same output buffer: after the wait only the
- * LAST call's result is readable (earlier calls leave nothing readable), and
- * a returned error may belong to any call since the previous wait (its
+ * read.
+ * Output buffers: consecutive calls alternate between two writer streams and
+ * two output buffers (the ctx's own, which the synchronous calls write, and a
+ * second of the same capacity), so two calls' writers run side by side and
+ * the stores do not pause while one ends and the next starts.  The second
+ * buffer costs one more result-sized allocation and is taken only when that
+ * capacity is at most half of the device memory free at the moment (checked by
+ * a call made with nothing pending, and again after a synchronous call grew
+ * the capacity); where it does not fit, its allocation fails, or
+ * cg_set_async_overlap(ctx, 0) was called, every call writes the one buffer on
+ * the ctx stream, as a synchronous call does.  Either way, after the wait only
+ * the LAST call's result is readable (earlier calls leave nothing readable):
+ * cg_result_device returns the buffer that call wrote, which differs from call
+ * to call -- its pointers are valid until the next expansion call, not beyond.
+ * cg_last_kernel_times [3] = the mean over those calls of the writer time:
+ * from the writer's start to its end, or, when the previous call's writer
+ * still ran on the other stream at that start, from that writer's end to this
+ * one's (0 if this one ended first).  These per-call intervals never overlap,
+ * so in a pipelined run [3] reads as completion-to-completion time per call.
+ * A returned error may belong to any call since the previous wait (its
  * message names the rule or the sizes).  *n_events is always set (0 when no
  * asynchronous call was made).  While calls are pending the result accessors
  * below refuse with CG_EINVAL.  A synchronous expansion (cg_expand,
@@ -291,7 +307,16 @@ int cg_expand_device(cg_ctx* ctx, const cg_specs* specs, const cg_zone* z, int64
 int cg_expand_device_async(cg_ctx* ctx, const cg_specs* specs, const cg_zone* z, int64_t t0,
                            int64_t t1);
 int cg_expand_wait(cg_ctx* ctx, int64_t* n_events);
-/* device pointers of the last device-resident result */
+/* on != 0 (default): pipelined calls alternate between two writer streams and
+ * output buffers when the second buffer fits (above); 0: one stream, one
+ * buffer, and the second buffer is freed.  Takes effect from the next
+ * cg_expand_device_async made with nothing pending; CG_EINVAL while calls are
+ * pending.  Results are the same either way.  (No reference counterpart: a
+ * memory-for-throughput knob.) */
+int cg_set_async_overlap(cg_ctx* ctx, int on);
+/* device pointers of the last device-resident result (valid until the next
+ * expansion call on this ctx; after pipelined calls d_times is the buffer the
+ * last call wrote) */
 int cg_result_device(cg_ctx* ctx, const int64_t** d_offsets, const int64_t** d_times,
                      int64_t* n_events);
 /* copy [first, first+count) of the last result's times to host */
@@ -299,7 +324,8 @@ int cg_result_copy_times(cg_ctx* ctx, int64_t first, int64_t count, int64_t* hos
 int cg_result_copy_offsets(cg_ctx* ctx, int64_t* host_offsets /* [R+1] */);
 
 /* Per-kernel device time of the last expansion (ms, HIP events on the ctx
- * stream): [0] count, [1] scan, [2] block map, [3] write (closed form),
+ * stream): [0] count, [1] scan, [2] block map, [3] write (closed form; after
+ * pipelined calls see cg_expand_device_async),
  * [4] write (walk), [5] offsets; of the last per-node call: [6] rule->node
  * join, [7] transpose (when the join is rebuilt) + segment records + per-node
  * offsets, [8] per-node write; [12] the last time-order pass; of the last
