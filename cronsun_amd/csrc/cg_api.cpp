@@ -1,5 +1,6 @@
 // cg_api.cpp -- the C-ABI of include/cronsun_gpu.h: contexts, device memory,
-// zones, spec upload, Next batches and the expansion pipeline.
+// zones, spec upload, plan packing, Next and lockTtl batches and the device
+// utilities (the expansion is cg_expand.cpp).
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
@@ -271,7 +272,7 @@ void cg_specs_free(cg_specs* s) {
 
 }  // extern "C"
 
-// ----------------------------------------------------------- plan upload
+// ----------------------------------------------------------- plan packing
 // one packed upload: when | off | segs | dtab
 PlanLayout plan_layout(const Plan& plan) {
   PlanLayout L;
@@ -316,13 +317,12 @@ int plan_args(const Plan& plan, const PlanLayout& L, char* base, int64_t t0, int
   return CG_OK;
 }
 
+// the plan of a Next / lockTtl batch into the ctx's plan_dev (an expansion
+// stages its own into its run set, cg_expand.cpp)
 int upload_plan(cg_ctx* c, const Plan& plan, int64_t t0, int64_t t1, PlanArgs* pa) {
   if (plan.segs.size() > size_t(kMaxSegments))
     return cg_fail(CG_ERANGE, "plan has more than " + std::to_string(kMaxSegments) +
                                   " segments (horizon too long for this zone)");
-  // plan_dev is shared by every entry point: whatever it held is gone, so the
-  // expansion's plan cache must not be trusted after this (expand re-validates)
-  c->plan_valid = false;
   const PlanLayout L = plan_layout(plan);
   std::vector<char>& h = c->plan_host;
   h.assign(L.bytes, 0);
@@ -409,262 +409,7 @@ int cg_lock_ttl_batch(cg_ctx* c, const cg_specs* s, const cg_zone* z, const int6
   return CG_OK;
 }
 
-}  // extern "C"
-
-// --------------------------------------------------------------- expansion
-// plan (cached) + k_count + scan of the run counts: c->run_off holds the run
-// offsets afterwards.  *empty = true when there is nothing to count.
-// map_cap > 0: the scan also builds k_write_cf's slice map in c->block_run
-// for an output capacity of map_cap events (no k_chunk_map launch).
-static int count_phase(cg_ctx* c, const cg_specs* s, const cg_zone* z, int64_t t0, int64_t t1,
-                       bool* empty, int64_t map_cap = 0) {
-  // no readable result until this call succeeds (the accessors check last_R/E).
-  // Asynchronous calls still pending are drained and their results and errors
-  // discarded: this call's result replaces them (cronsun_gpu.h).
-  int rc0 = async_drain(c);
-  if (rc0) return rc0;
-  c->async_rc = 0;
-  c->async_msg.clear();
-  if ((rc0 = pn_async_drain(c))) return rc0;  // the same for pipelined per-node windows
-  c->pa_rc = 0;
-  c->pa_msg.clear();
-  c->pa_last = -1;
-  c->pa_en_sum = 0;
-  c->as_last = -1;
-  c->times_last = 0;  // synchronous calls write c->times
-  c->last_R = 0;
-  c->last_E = 0;
-  HIPCHK(hipSetDevice(c->device));
-  if (t1 - t0 > CG_MAX_HORIZON || t0 < -(int64_t(1) << 45) || t1 > (int64_t(1) << 45))
-    return cg_fail(CG_ERANGE, "horizon must satisfy t1 - t0 <= CG_MAX_HORIZON (40 years)");
-  const int64_t R = int64_t(s->n);
-  int rc;
-  // plan (cached across identical calls)
-  if (!(c->plan_valid && c->plan_zone == z->serial && c->plan_t0 == t0 && c->plan_t1 == t1)) {
-    c->plan = build_plan(z->rules, t0, t1);
-    if ((rc = upload_plan(c, c->plan, t0, t1, &c->pa))) {
-      c->plan_valid = false;
-      return rc;
-    }
-    c->plan_valid = true;
-    c->plan_zone = z->serial;
-    c->plan_t0 = t0;
-    c->plan_t1 = t1;
-  }
-  const PlanArgs& pa = c->pa;
-  const int64_t G = pa.G;
-  c->last_G = G;
-  for (int i = 0; i < 6; i++) c->kt[i] = 0;
-  if ((rc = c->offsets.ensure(R + 1))) return rc;
-  if (R == 0 || G == 0) {
-    HIPCHK(hipMemsetAsync(c->offsets.p, 0, (R + 1) * 8, c->st));
-    HIPCHK(hipStreamSynchronize(c->st));
-    *empty = true;
-    return CG_OK;
-  }
-  const int64_t nruns = R * G;
-  if ((rc = c->run_anchor.ensure(nruns))) return rc;
-  if ((rc = c->run_count.ensure(nruns))) return rc;
-  if ((rc = c->run_dmask.ensure(nruns))) return rc;
-  if ((rc = c->run_off.ensure(nruns + 1))) return rc;
-  if ((rc = c->scan_tmp.ensure(scan_temp_bytes(nruns)))) return rc;
-
-  if ((rc = c->stuck.ensure(1))) return rc;
-  if (!c->res_host) {
-    // mapped, coherent pinned memory: the scan kernel stores the 16-B record
-    // straight into it (no D2H copy launch); read after the stream sync
-    HIPCHK(hipHostMalloc(reinterpret_cast<void**>(&c->res_host), 16,
-                         hipHostMallocMapped | hipHostMallocCoherent));
-    HIPCHK(hipHostGetDevicePointer(reinterpret_cast<void**>(&c->res_dev), c->res_host, 0));
-  }
-  if (!c->stuck_armed) HIPCHK(hipMemsetAsync(c->stuck.p, 0xFF, sizeof(unsigned long long), c->st));
-  c->stuck_armed = false;  // until this call's scan re-arms it
-  const bool all_phases = c->phase_timing >= 2;
-  if (all_phases) (void)hipEventRecord(c->ev[0], c->st);
-  launch_count(s->d, R, pa, c->run_anchor.p, c->run_count.p, c->run_dmask.p, c->stuck.p, c->st);
-  if (all_phases) (void)hipEventRecord(c->ev[1], c->st);
-  if (map_cap > 0 && (rc = c->block_run.ensure(slice_map_words(map_cap)))) return rc;
-  launch_scan_runs(c->run_count.p, c->run_off.p, R, int32_t(G), c->scan_tmp.p, c->offsets.p, c->res_dev,
-                   c->stuck.p, map_cap > 0 ? c->block_run.p : nullptr, map_cap, c->st);
-  if (all_phases) (void)hipEventRecord(c->ev[2], c->st);
-  HIPCHK(hipGetLastError());
-  *empty = false;
-  return CG_OK;
-}
-
-static int stuck_error(unsigned long long stuck) {
-  return cg_fail(CG_ERANGE, "rule " + std::to_string(stuck) +
-                                ": the reference Next loop never terminates inside this horizon "
-                                "(Next does not return, or returns a time <= its input and cycles)");
-}
-
-int expand_device_locked(cg_ctx* c, const cg_specs* s, const cg_zone* z, int64_t t0, int64_t t1,
-                         int64_t* n_events) {
-  bool empty = true;
-  // steady state: the output buffer exists, so the scan builds the writer's
-  // slice map for its capacity (a first or a growing call maps separately)
-  const int64_t cap0 = int64_t(c->times.cap);
-  int rc = count_phase(c, s, z, t0, t1, &empty, cap0);
-  if (rc) return rc;
-  const int64_t R = int64_t(s->n);
-  if (empty) {
-    c->last_R = R;  // offsets are all zero
-    c->last_E = 0;
-    *n_events = 0;
-    return CG_OK;
-  }
-  const PlanArgs& pa = c->pa;
-  const int64_t G = pa.G;
-  const int64_t nruns = R * G;
-  // Write phase without a host round trip: the chunk map and writers read the
-  // event total from device memory and size their work from it.  Output
-  // capacity comes from earlier calls; the first call (or a larger result)
-  // syncs once to size the buffers and relaunches the write phase.
-  if (c->times.cap == 0) {
-    int64_t E0 = 0;
-    HIPCHK(hipMemcpyAsync(&E0, c->run_off.p + nruns, 8, hipMemcpyDeviceToHost, c->st));
-    HIPCHK(hipStreamSynchronize(c->st));
-    if ((rc = c->times.ensure(std::max<int64_t>(E0, 1)))) return rc;
-  }
-  // walked runs: WALK windows, or CF segments whose entry fire does not fully
-  // match (only possible when the plan has zone transitions)
-  const bool all_phases = c->phase_timing >= 2;
-  // (a CF run is entered by the exact walk only after a WALK segment, or from
-  // T0 when a transition lies in the 40 days before it)
-  const bool has_walk = (c->plan.flags & (kPlanT0Walk | kPlanWalkSegs)) != 0;
-  int64_t E = 0;
-  unsigned long long stuck = 0;
-  for (int attempt = 0; attempt < 2; attempt++) {
-    const int64_t cap = int64_t(c->times.cap);
-    if ((rc = c->block_run.ensure(slice_map_words(cap)))) return rc;
-    if (all_phases) (void)hipEventRecord(c->ev[3], c->st);
-    if (!(cap0 > 0 && cap == cap0))
-      launch_chunk_map(c->run_off.p, nruns, cap, c->block_run.p, c->st);
-    (void)hipEventRecord(c->ev[4], c->st);
-    launch_write_cf(s->d, pa, c->run_anchor.p, c->run_count.p, c->run_dmask.p, c->run_off.p, nruns,
-                    c->block_run.p, cap, c->times.p, c->write_blocks, c->st);
-    (void)hipEventRecord(c->ev[5], c->st);
-    if (has_walk)
-      launch_write_walk(s->d, R, pa, c->run_anchor.p, c->run_count.p, c->run_dmask.p,
-                        c->run_off.p, cap, c->times.p, c->st);
-    if (all_phases) (void)hipEventRecord(c->ev[6], c->st);
-    HIPCHK(hipGetLastError());
-    HIPCHK(hipStreamSynchronize(c->st));
-    c->stuck_armed = true;
-    E = c->res_host[0];
-    stuck = static_cast<unsigned long long>(c->res_host[1]);
-    if (stuck != ~0ULL) return stuck_error(stuck);
-    if (E <= cap) break;
-    if ((rc = c->times.ensure(E))) return rc;  // grow and redo the write phase
-  }
-  (void)hipEventElapsedTime(&c->kt[3], c->ev[4], c->ev[5]);
-  if (all_phases) {
-    (void)hipEventElapsedTime(&c->kt[0], c->ev[0], c->ev[1]);
-    (void)hipEventElapsedTime(&c->kt[1], c->ev[1], c->ev[2]);
-    (void)hipEventElapsedTime(&c->kt[2], c->ev[3], c->ev[4]);
-    (void)hipEventElapsedTime(&c->kt[4], c->ev[5], c->ev[6]);
-    c->kt[5] = 0.f;  // per-rule offsets: written by the scan (k_scan_apply)
-  } else {
-    c->kt[0] = c->kt[1] = c->kt[2] = c->kt[4] = c->kt[5] = -1.f;
-  }
-  c->last_R = R;
-  c->last_E = E;
-  *n_events = E;
-  return CG_OK;
-}
-
-extern "C" int cg_count(cg_ctx* c, const cg_specs* s, const cg_zone* z, int64_t t0, int64_t t1,
-                        int64_t* counts, int64_t* total) {
-  if (!c || !s || !z || !total || (s->n && !counts)) return cg_fail(CG_EINVAL, "cg_count: null");
-  std::lock_guard<std::mutex> g(c->mu);
-  (void)hipGetLastError();
-  bool empty = true;
-  int rc = count_phase(c, s, z, t0, t1, &empty);
-  if (rc) return rc;
-  const int64_t R = int64_t(s->n);
-  if (empty) {
-    for (int64_t r = 0; r < R; r++) counts[r] = 0;
-    *total = 0;
-    return CG_OK;
-  }
-  HIPCHK(hipGetLastError());
-  std::vector<int64_t> off(size_t(R) + 1);
-  HIPCHK(hipMemcpyAsync(off.data(), c->offsets.p, (R + 1) * 8, hipMemcpyDeviceToHost, c->st));
-  HIPCHK(hipStreamSynchronize(c->st));
-  c->stuck_armed = true;
-  const unsigned long long stuck = static_cast<unsigned long long>(c->res_host[1]);
-  if (stuck != ~0ULL) return stuck_error(stuck);
-  for (int64_t r = 0; r < R; r++) counts[r] = off[size_t(r) + 1] - off[size_t(r)];
-  *total = off[size_t(R)];
-  return CG_OK;  // (no expansion result to read after a count: last_R = last_E = 0)
-}
-
-extern "C" {
-
-int cg_expand_device(cg_ctx* c, const cg_specs* s, const cg_zone* z, int64_t t0, int64_t t1,
-                     int64_t* n_events) {
-  if (!c || !s || !z || !n_events) return cg_fail(CG_EINVAL, "cg_expand_device: null");
-  std::lock_guard<std::mutex> g(c->mu);
-  (void)hipGetLastError();  // clear a stale error so launch checks see only their own
-  return expand_device_locked(c, s, z, t0, t1, n_events);
-}
-
-int cg_expand(cg_ctx* c, const cg_specs* s, const cg_zone* z, int64_t t0, int64_t t1,
-              cg_csr* out) {
-  if (!c || !s || !z || !out) return cg_fail(CG_EINVAL, "cg_expand: null");
-  std::lock_guard<std::mutex> g(c->mu);
-  (void)hipGetLastError();  // clear a stale error so launch checks see only their own
-  int64_t E = 0;
-  int rc = expand_device_locked(c, s, z, t0, t1, &E);
-  if (rc) return rc;
-  out->n_events = E;
-  if (out->offsets)
-    HIPCHK(hipMemcpy(out->offsets, c->offsets.p, (s->n + 1) * 8, hipMemcpyDeviceToHost));
-  if (out->times) {
-    if (out->times_cap < E) return cg_fail(CG_ECAPACITY, "times buffer too small; see n_events");
-    if (E) HIPCHK(hipMemcpy(out->times, c->times.p, E * 8, hipMemcpyDeviceToHost));
-  }
-  return CG_OK;
-}
-
-static int refuse_pending(cg_ctx* c, const char* what) {
-  if (!async_pending(c)) return CG_OK;
-  return cg_fail(CG_EINVAL, std::string(what) + ": asynchronous expansions pending (call cg_expand_wait first)");
-}
-
-int cg_result_device(cg_ctx* c, const int64_t** d_off, const int64_t** d_times, int64_t* n) {
-  if (!c) return cg_fail(CG_EINVAL, "cg_result_device: null");
-  std::lock_guard<std::mutex> g(c->mu);
-  if (int rc = refuse_pending(c, "cg_result_device")) return rc;
-  if (d_off) *d_off = c->as_last >= 0 ? c->as[c->as_last].offsets.p : c->offsets.p;
-  if (d_times) *d_times = c->result_times();
-  if (n) *n = c->last_E;
-  return CG_OK;
-}
-
-int cg_result_copy_times(cg_ctx* c, int64_t first, int64_t count, int64_t* host) {
-  if (!c || (count && !host)) return cg_fail(CG_EINVAL, "cg_result_copy_times: null");
-  std::lock_guard<std::mutex> g(c->mu);
-  if (int rc = refuse_pending(c, "cg_result_copy_times")) return rc;
-  if (first < 0 || count < 0 || first + count > c->last_E)
-    return cg_fail(CG_EINVAL, "range outside the last result");
-  (void)hipGetLastError();  // clear a stale error so launch checks see only their own
-  HIPCHK(hipSetDevice(c->device));
-  if (count) HIPCHK(hipMemcpy(host, c->result_times() + first, count * 8, hipMemcpyDeviceToHost));
-  return CG_OK;
-}
-
-int cg_result_copy_offsets(cg_ctx* c, int64_t* host) {
-  if (!c || !host) return cg_fail(CG_EINVAL, "cg_result_copy_offsets: null");
-  std::lock_guard<std::mutex> g(c->mu);
-  if (int rc = refuse_pending(c, "cg_result_copy_offsets")) return rc;
-  (void)hipGetLastError();  // clear a stale error so launch checks see only their own
-  HIPCHK(hipSetDevice(c->device));
-  const int64_t* off = c->as_last >= 0 ? c->as[c->as_last].offsets.p : c->offsets.p;
-  HIPCHK(hipMemcpy(host, off, (c->last_R + 1) * 8, hipMemcpyDeviceToHost));
-  return CG_OK;
-}
-
+// -------------------------------------------------------------- utilities
 int cg_checksum_device(cg_ctx* c, const void* d_ptr, int64_t n, int elem_bytes, int64_t first_index,
                        int64_t add, uint64_t* out) {
   if (!c || !out || (n > 0 && !d_ptr) || n < 0 || (elem_bytes != 8 && elem_bytes != 4))

@@ -1,4 +1,8 @@
-// cg_api_internal.h -- context/specs objects behind the C-ABI handles.
+// cg_api_internal.h -- context/specs objects behind the C-ABI handles, and the
+// state the expansion paths share: RunSet (a rule-major count/scan/write chain
+// with its plan; one for the synchronous path, one per pipelined set) and
+// PnWindow (a per-node window's chain), each owned once by cg_ctx and once by
+// every set of the matching pipeline (AsyncSet, PnAsyncSet).
 #pragma once
 #include <hip/hip_runtime.h>
 
@@ -94,33 +98,50 @@ struct RulesStore {
   }
 };
 
-// One run set of the pipelined expansion (cg_expand_device_async): what the
-// count/scan of a call writes and its writer reads, so the count/scan of call
-// k (on the ctx's second stream) can run while the writer of call k-1 does.
-struct AsyncSet {
+// One run set of the rule-major expansion (cg_expand.cpp): what the count and
+// scan of a call write and its writer reads, with the call's plan.  The
+// synchronous path has one (cg_ctx::rs), every pipelined set its own, so the
+// count and scan of call k (on the ctx's second stream) can run while the
+// writer of call k-1 reads another.
+struct RunSet {
   DBuf<int64_t> run_anchor, run_off, offsets, block_run;
   DBuf<int32_t> run_count;
   DBuf<uint32_t> run_dmask;
   DBuf<char> scan_tmp, plan_dev;
   DBuf<unsigned long long> stuck;
-  int64_t* res_host = nullptr;  // {E, stuck rule}: mapped pinned, written by the scan
+  // {E, stuck rule}: mapped, coherent pinned memory the scan kernel stores
+  // straight into (no D2H copy launch); read once the scan's stream has drained
+  int64_t* res_host = nullptr;
   int64_t* res_dev = nullptr;
   char* plan_pin = nullptr;  // pinned staging of the plan upload
   size_t plan_pin_cap = 0;
+  // the plan in plan_dev, kept across calls with the same (zone, t0, t1)
   cg::Plan plan;
   cg::PlanArgs pa{};
   bool plan_valid = false;
   uint64_t plan_zone = 0;
   int64_t plan_t0 = 0, plan_t1 = 0;
-  hipEvent_t written = nullptr;  // recorded behind the walk writer
-  // the set's writer-done event of its last call: `written`, or without a walk
-  // kernel the call's end-of-writer timing event (not owned; null: none yet)
-  hipEvent_t done = nullptr;
-  int tslot = 0;   // the call's pair in the ctx's timing-event ring
-  int tprev = -1;  // the previous call's pair when its writer may overlap this one's (-1: none)
-  bool pending = false;  // a call on this set whose record has not been checked
-  bool armed = false;    // stuck flag holds ~0 (set once; every scan re-arms it)
-  int64_t R = 0, cap = 0;
+  // The stuck word holds ~0 whenever a count starts: k_count only lowers it
+  // (atomicMin of a stuck rule) and the scan behind it copies it into the
+  // record and stores ~0 again.  run_set_count_scan sets it once, before the
+  // set's first count, and from then on never returns between enqueueing a
+  // count and its scan (every allocation comes first), so every count that was
+  // enqueued has a scan behind it that re-arms the word.
+  bool armed = false;
+  int64_t R = 0, cap = 0;  // rules and slice-map capacity of the last count and scan
+  // walked runs: WALK windows, or CF segments whose entry fire does not fully
+  // match (only possible when the plan has zone transitions; a CF run is
+  // entered by the exact walk only after a WALK segment, or from T0 when a
+  // transition lies in the 40 days before it)
+  bool has_walk() const { return (plan.flags & (cg::kPlanT0Walk | cg::kPlanWalkSegs)) != 0; }
+  int ensure_res() {
+    if (res_host) return CG_OK;
+    HIPCHK(hipHostMalloc(reinterpret_cast<void**>(&res_host), 16, hipHostMallocMapped | hipHostMallocCoherent));
+    HIPCHK(hipHostGetDevicePointer(reinterpret_cast<void**>(&res_dev), res_host, 0));
+    res_host[0] = 0;
+    res_host[1] = -1;
+    return CG_OK;
+  }
   void release() {
     run_anchor.release(); run_off.release(); offsets.release(); block_run.release();
     run_count.release(); run_dmask.release(); scan_tmp.release(); plan_dev.release(); stuck.release();
@@ -129,6 +150,22 @@ struct AsyncSet {
     res_host = res_dev = nullptr;
     plan_pin = nullptr;
     plan_pin_cap = 0;
+  }
+};
+
+// One set of the pipelined expansion (cg_expand_device_async): a run set and
+// the bookkeeping of the call that last used it.
+struct AsyncSet {
+  RunSet rs;
+  hipEvent_t written = nullptr;  // recorded behind the walk writer
+  // the set's writer-done event of its last call: `written`, or without a walk
+  // kernel the call's end-of-writer timing event (not owned; null: none yet)
+  hipEvent_t done = nullptr;
+  int tslot = 0;   // the call's pair in the ctx's timing-event ring
+  int tprev = -1;  // the previous call's pair when its writer may overlap this one's (-1: none)
+  bool pending = false;  // a call on this set whose record has not been checked
+  void release() {
+    rs.release();
     if (written) (void)hipEventDestroy(written), written = nullptr;
     done = nullptr;
   }
@@ -175,7 +212,7 @@ struct PnWindow {
 // chain, so window k+1's expansion and records are built on the second stream
 // while window k's per-node writer streams on the first.
 struct PnAsyncSet {
-  AsyncSet rm;
+  RunSet rm;
   PnWindow w;
   DBuf<int64_t> times, node_off;
   DBuf<char> seg_tmp;
@@ -214,29 +251,22 @@ struct cg_ctx {
   // stack, so throughput runs use 1 (cg_set_phase_timing).
   int phase_timing = 2;
 
-  // plan cache
-  cg::Plan plan;
-  cg::PlanArgs pa{};
-  bool plan_valid = false;
-  uint64_t plan_zone = 0;
-  int64_t plan_t0 = 0, plan_t1 = 0;
+  // the zone table of a Next / lockTtl batch (upload_plan)
   std::vector<char> plan_host;
   DBuf<char> plan_dev;
 
-  // expansion buffers
-  DBuf<int64_t> run_anchor, run_off, offsets, times, block_run, nb_in, nb_out, lt_avg;
-  DBuf<int32_t> run_count, lt_kind;
-  DBuf<uint32_t> run_dmask;
+  // synchronous expansion: its run set and the output (the pipelined path's
+  // first output buffer too); Next / lockTtl batches; the shared temporary of
+  // the join, transpose, segment and time-order scans
+  RunSet rs;
+  DBuf<int64_t> times, nb_in, nb_out, lt_avg;
+  DBuf<int32_t> lt_kind;
   DBuf<char> scan_tmp;
-  DBuf<unsigned long long> stuck;  // ~0 between calls (the expansion scan re-arms it)
   DBuf<unsigned long long> cksum;  // cg_checksum_device accumulator
-  bool stuck_armed = false;        // false: memset it before the next k_count
-  int64_t* res_host = nullptr;     // {E, stuck rule}: mapped pinned 16 B the scan writes
-  int64_t* res_dev = nullptr;      // res_host's device address
-  int64_t last_E = 0, last_R = 0, last_G = 0;
+  int64_t last_E = 0, last_R = 0;
 
-  // pipelined expansion (cg_async.cpp): two run sets used in turn, count +
-  // scan on st_cs, writers on st; as_last = set of the last async result
+  // pipelined expansion (cg_async.cpp): the sets used in turn, count + scan
+  // on st_cs, writers on st / st_w1; as_last = set of the last async result
   // (-1: the last result came from the synchronous path)
   // Three run sets: a call's count and scan are enqueued while the writer
   // two calls back is long done, so they sit ready in the hardware queue and
@@ -342,13 +372,9 @@ struct cg_ctx {
     if (st_ot) (void)hipStreamDestroy(st_ot);
     st_ot = nullptr;
     plan_dev.release();
-    run_anchor.release(); run_off.release(); offsets.release(); times.release();
-    block_run.release(); nb_in.release(); nb_out.release(); run_count.release();
-    lt_avg.release(); lt_kind.release();
-    if (res_host) (void)hipHostFree(res_host);
-    res_host = nullptr;
-    res_dev = nullptr;
-    run_dmask.release(); scan_tmp.release(); stuck.release(); cksum.release();
+    rs.release(); times.release();
+    nb_in.release(); nb_out.release(); lt_avg.release(); lt_kind.release();
+    scan_tmp.release(); cksum.release();
     rn_off.release(); node_off.release(); node_time.release(); nt_off.release(); rs_off.release();
     seg_pair.release(); rn_cnt.release(); rn_nodes.release();
     pair_node.release(); pair_rule.release(); node_rule.release(); nt_rule.release();
@@ -387,16 +413,32 @@ PlanLayout plan_layout(const cg::Plan& plan);
 void plan_pack(const cg::Plan& plan, const PlanLayout& L, char* dst);
 int plan_args(const cg::Plan& plan, const PlanLayout& L, char* dev_base, int64_t t0, int64_t t1,
               cg::PlanArgs* pa);
+// The rule-major chain every expansion entry point runs (cg_expand.cpp).
+// run_set_count_scan stages the plan of (t0, t1] in zone z into rs (cached per
+// (zone, t0, t1); through the set's pinned buffer, no stream sync) and
+// enqueues k_count and the scan of the run counts on st: rs.run_off then holds
+// the run offsets, rs.offsets the rule offsets and the set's record {E, stuck
+// rule}.  map_cap > 0: the scan also builds k_write_cf's slice map for an
+// output capacity of map_cap events (no k_chunk_map launch).  ev (or null):
+// three events recorded before the count, between the two and after the scan.
+// *empty: no rule or no segment -- nothing is counted, the record reads {0,
+// none} and rs.offsets [R+1] is left for the caller to zero.  The caller has
+// made sure that nothing enqueued earlier still reads or writes rs.
+int run_set_count_scan(RunSet& rs, const cg_specs* s, const cg_zone* z, int64_t t0, int64_t t1, int64_t map_cap,
+                       hipStream_t st, hipEvent_t* ev, bool* empty);
+// the writers of the runs counted last into out (cap events: the capacity the
+// slice map was built for), on st: k_write_cf on `blocks` blocks, after_cf (or
+// null) recorded behind it, then k_write_walk when the plan has walked runs
+void run_set_write_enqueue(const RunSet& rs, const cg_specs* s, int64_t cap, int64_t* out, int blocks,
+                           hipStream_t st, hipEvent_t after_cf = nullptr);
+// the error text of a record whose stuck rule is not ~0
+std::string stuck_msg(unsigned long long rule);
 int expand_device_locked(cg_ctx* c, const cg_specs* s, const cg_zone* z, int64_t t0, int64_t t1,
                          int64_t* n_events);
 // finish and check every pending cg_expand_device_async call (cg_async.cpp);
 // their errors are reported by the next cg_expand_wait
 int async_drain(cg_ctx* c);
-int ensure_async(cg_ctx* c);  // the second stream and the run sets' events / pinned records
-// stage a call's plan into run set a and enqueue its count + scan on the second
-// stream (cg_async.cpp); *empty when there is nothing to count
-int async_count_scan(cg_ctx* c, AsyncSet& a, const cg_specs* s, const cg_zone* z, int64_t t0, int64_t t1,
-                     int64_t cap, bool* empty);
+int ensure_async(cg_ctx* c);  // the second stream and the pipelined sets' events
 bool async_pending(const cg_ctx* c);
 // pipelined per-node calls (cg_pernode.hip): drain (errors kept for the next
 // wait) / any pending

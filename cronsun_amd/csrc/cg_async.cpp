@@ -14,10 +14,18 @@
 // the device waits for another kernel.  Where the second buffer does not fit (or
 // cg_set_async_overlap(0)) every writer runs on the ctx stream into c->times.
 // The plan of each call (zone table, segments, day table) is staged through
-// pinned memory of its run set, so a moving T0 costs no stream sync either.  cg_expand_wait drains the pipeline
-// and reports the calls' errors: a rule whose reference Next loop never ends
-// (CG_ERANGE), or a result larger than the output capacity sized by an
-// earlier synchronous call (CG_ECAPACITY: the writer then wrote nothing).
+// pinned memory of its run set, so a moving T0 costs no stream sync either.
+// cg_expand_wait drains the pipeline and reports the calls' errors: a rule
+// whose reference Next loop never ends (CG_ERANGE), or a result larger than
+// the output capacity sized by an earlier synchronous call (CG_ECAPACITY: the
+// writer then wrote nothing).
+//
+// The plan staging, count, scan and writers themselves are the run-set chain
+// of cg_expand.cpp (run_set_count_scan / run_set_write_enqueue), the one the
+// synchronous calls run on the ctx stream.  This file is the pipeline around
+// it: which set, stream and output buffer a call gets (AsyncSet holds a
+// RunSet and the bookkeeping of the call that last used it), the events that
+// order and time the writers, and the checking of finished calls.
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
@@ -54,18 +62,16 @@ void check_set(cg_ctx* c, AsyncSet& a) {
     c->wr_ms_sum += ms;
     c->wr_n++;
   }
-  const int64_t E = a.res_host[0];
-  const unsigned long long stuck = static_cast<unsigned long long>(a.res_host[1]);
+  const int64_t E = a.rs.res_host[0];
+  const unsigned long long stuck = static_cast<unsigned long long>(a.rs.res_host[1]);
   if (c->async_rc) return;  // keep the first error
   if (stuck != ~0ULL) {
     c->async_rc = CG_ERANGE;
-    c->async_msg = "rule " + std::to_string(stuck) +
-                   ": the reference Next loop never terminates inside this horizon "
-                   "(Next does not return, or returns a time <= its input and cycles)";
-  } else if (E > a.cap) {
+    c->async_msg = stuck_msg(stuck);
+  } else if (E > a.rs.cap) {
     c->async_rc = CG_ECAPACITY;
     c->async_msg = "async expansion: " + std::to_string(E) + " events exceed the output capacity " +
-                   std::to_string(a.cap) + " (run a synchronous cg_expand_device to grow it)";
+                   std::to_string(a.rs.cap) + " (run a synchronous cg_expand_device to grow it)";
   }
 }
 
@@ -75,13 +81,7 @@ int ensure_async(cg_ctx* c) {
   if (c->st_cs) return CG_OK;
   HIPCHK(hipStreamCreateWithFlags(&c->st_cs, hipStreamNonBlocking));
   for (hipEvent_t& e : c->cs_done) HIPCHK(hipEventCreateWithFlags(&e, hipEventDisableTiming));
-  for (AsyncSet& a : c->as) {
-    HIPCHK(hipEventCreateWithFlags(&a.written, hipEventDisableTiming));
-    HIPCHK(hipHostMalloc(reinterpret_cast<void**>(&a.res_host), 16, hipHostMallocMapped | hipHostMallocCoherent));
-    HIPCHK(hipHostGetDevicePointer(reinterpret_cast<void**>(&a.res_dev), a.res_host, 0));
-    a.res_host[0] = 0;
-    a.res_host[1] = -1;
-  }
+  for (AsyncSet& a : c->as) HIPCHK(hipEventCreateWithFlags(&a.written, hipEventDisableTiming));
   for (hipEvent_t* ring : {c->tw0, c->tw1})
     for (int i = 0; i < cg_ctx::kTimeRing; i++) HIPCHK(hipEventCreateWithFlags(&ring[i], hipEventDisableSystemFence));
   return CG_OK;
@@ -141,59 +141,6 @@ int async_drain(cg_ctx* c) {
   return CG_OK;
 }
 
-// Stages call (t0, t1]'s plan into run set a (pinned memory, no stream sync)
-// and enqueues its count and scan on the ctx's second stream, building the
-// writer's slice map for an output capacity of cap events.  *empty: R or G
-// is 0 (nothing enqueued).
-int async_count_scan(cg_ctx* c, AsyncSet& a, const cg_specs* s, const cg_zone* z, int64_t t0, int64_t t1,
-                     int64_t cap, bool* empty) {
-  int rc;
-  const int64_t R = int64_t(s->n);
-  if (!(a.plan_valid && a.plan_zone == z->serial && a.plan_t0 == t0 && a.plan_t1 == t1)) {
-    a.plan_valid = false;
-    a.plan = build_plan(z->rules, t0, t1);
-    const PlanLayout L = plan_layout(a.plan);
-    if (a.plan_pin_cap < L.bytes) {
-      if (a.plan_pin) (void)hipHostFree(a.plan_pin);
-      a.plan_pin = nullptr;
-      a.plan_pin_cap = 0;
-      HIPCHK(hipHostMalloc(reinterpret_cast<void**>(&a.plan_pin), L.bytes));
-      a.plan_pin_cap = L.bytes;
-    }
-    plan_pack(a.plan, L, a.plan_pin);
-    if ((rc = a.plan_dev.ensure(L.bytes))) return rc;
-    if ((rc = plan_args(a.plan, L, a.plan_dev.p, t0, t1, &a.pa))) return rc;
-    HIPCHK(hipMemcpyAsync(a.plan_dev.p, a.plan_pin, L.bytes, hipMemcpyHostToDevice, c->st_cs));
-    a.plan_valid = true;
-    a.plan_zone = z->serial;
-    a.plan_t0 = t0;
-    a.plan_t1 = t1;
-  }
-  const PlanArgs& pa = a.pa;
-  const int64_t G = pa.G;
-  if ((rc = a.offsets.ensure(R + 1))) return rc;
-  if (R == 0 || G == 0) {
-    *empty = true;
-    return CG_OK;
-  }
-  const int64_t nruns = R * G;
-  if ((rc = a.run_anchor.ensure(nruns)) || (rc = a.run_count.ensure(nruns)) || (rc = a.run_dmask.ensure(nruns)) ||
-      (rc = a.run_off.ensure(nruns + 1)) || (rc = a.scan_tmp.ensure(scan_temp_bytes(nruns))) ||
-      (rc = a.block_run.ensure(slice_map_words(cap))) || (rc = a.stuck.ensure(1)))
-    return rc;
-  // count + scan on the second stream (the scan re-arms the stuck flag and
-  // builds the writer's slice map for the output capacity)
-  if (!a.armed) HIPCHK(hipMemsetAsync(a.stuck.p, 0xFF, sizeof(unsigned long long), c->st_cs));
-  a.armed = true;  // from here on every scan re-arms it
-  launch_count(s->d, R, pa, a.run_anchor.p, a.run_count.p, a.run_dmask.p, a.stuck.p, c->st_cs);
-  launch_scan_runs(a.run_count.p, a.run_off.p, R, int32_t(G), a.scan_tmp.p, a.offsets.p, a.res_dev, a.stuck.p,
-                   a.block_run.p, cap, c->st_cs);
-  a.R = R;
-  a.cap = cap;
-  *empty = false;
-  return CG_OK;
-}
-
 extern "C" {
 
 int cg_expand_device_async(cg_ctx* c, const cg_specs* s, const cg_zone* z, int64_t t0, int64_t t1) {
@@ -225,24 +172,21 @@ int cg_expand_device_async(cg_ctx* c, const cg_specs* s, const cg_zone* z, int64
   if (wi) c->w1_dirty = true;
   const int64_t R = int64_t(s->n);
   bool empty = false;
-  if ((rc = async_count_scan(c, a, s, z, t0, t1, cap, &empty))) return rc;
+  // count + scan on the second stream (the scan builds the writer's slice map
+  // for the output capacity)
+  if ((rc = run_set_count_scan(a.rs, s, z, t0, t1, cap, c->st_cs, nullptr, &empty))) return rc;
   if (empty) {  // nothing to count: zero offsets, an empty result
-    HIPCHK(hipMemsetAsync(a.offsets.p, 0, (R + 1) * 8, sw));
-    a.res_host[0] = 0;
-    a.res_host[1] = -1;
-    a.R = R;
+    HIPCHK(hipMemsetAsync(a.rs.offsets.p, 0, (R + 1) * 8, sw));
     c->as_next = (k + 1) % cg_ctx::kAsyncSets;
     c->as_last = k;
     c->last_R = R;
     c->last_E = 0;
     return CG_OK;
   }
-  const PlanArgs& pa = a.pa;
-  const int64_t nruns = R * int64_t(pa.G);
   HIPCHK(hipEventRecord(c->cs_done[k], c->st_cs));
   // the writer after the last one on its stream, once this call's scan is done
   HIPCHK(hipStreamWaitEvent(sw, c->cs_done[k], 0));
-  const bool has_walk = (a.plan.flags & (kPlanT0Walk | kPlanWalkSegs)) != 0;
+  const bool has_walk = a.rs.has_walk();
   // with a writer of this batch possibly still running on the other stream the
   // two share the CUs: the smaller grid (the first writer after a drain runs
   // alone at its start and keeps the full one)
@@ -252,11 +196,7 @@ int cg_expand_device_async(cg_ctx* c, const cg_specs* s, const cg_zone* z, int64
   c->tw_prev = a.tslot;
   c->tw_next = (a.tslot + 1) % cg_ctx::kTimeRing;
   (void)hipEventRecord(c->tw0[a.tslot], sw);
-  launch_write_cf(s->d, pa, a.run_anchor.p, a.run_count.p, a.run_dmask.p, a.run_off.p, nruns, a.block_run.p, cap,
-                  out, blocks, sw);
-  (void)hipEventRecord(c->tw1[a.tslot], sw);
-  if (has_walk)
-    launch_write_walk(s->d, R, pa, a.run_anchor.p, a.run_count.p, a.run_dmask.p, a.run_off.p, cap, out, sw);
+  run_set_write_enqueue(a.rs, s, cap, out, blocks, sw, c->tw1[a.tslot]);
   // the set is free again once its writer is done: without a walk that is the
   // end-of-writer event (one event packet fewer behind the writer; its ring
   // pair is re-recorded only after the set's next use has waited for it)
@@ -266,8 +206,6 @@ int cg_expand_device_async(cg_ctx* c, const cg_specs* s, const cg_zone* z, int64
     a.done = a.written;
   }
   HIPCHK(hipGetLastError());
-  a.R = R;
-  a.cap = cap;
   a.pending = true;
   c->as_next = (k + 1) % cg_ctx::kAsyncSets;
   c->as_last = k;
@@ -295,9 +233,10 @@ int cg_expand_wait(cg_ctx* c, int64_t* n_events) {
   c->async_msg.clear();
   int64_t E = 0;
   if (c->as_last >= 0) {
-    E = c->as[c->as_last].res_host[0];
+    const RunSet& rs = c->as[c->as_last].rs;
+    E = rs.res_host[0];
     c->last_E = rc_async ? 0 : E;
-    c->last_R = rc_async ? 0 : c->as[c->as_last].R;
+    c->last_R = rc_async ? 0 : rs.R;
   }
   if (n_events) *n_events = E;  // 0 when no asynchronous call was made since the last synchronous one
   if (rc_async) return cg_fail(rc_async, msg);

@@ -705,8 +705,8 @@ int per_node_locked(cg_ctx* c, const cg_specs* s, const cg_zone* z, int64_t t0, 
     if ((rc = c->cksum.ensure(1))) return rc;
     for (;;) {
       HIPCHK(hipMemsetAsync(c->cksum.p, 0, 8, st));
-      hipLaunchKernelGGL(k_band_max, dim3(gridn((R + B - 1) / B, 256, 1 << 30)), dim3(256), 0, st, c->offsets.p, R,
-                         B, c->cksum.p);
+      hipLaunchKernelGGL(k_band_max, dim3(gridn((R + B - 1) / B, 256, 1 << 30)), dim3(256), 0, st,
+                         c->rs.offsets.p, R, B, c->cksum.p);
       unsigned long long mx = 0;
       HIPCHK(hipMemcpyAsync(&mx, c->cksum.p, 8, hipMemcpyDeviceToHost, st));
       HIPCHK(hipStreamSynchronize(st));
@@ -727,7 +727,7 @@ int per_node_locked(cg_ctx* c, const cg_specs* s, const cg_zone* z, int64_t t0, 
   PnWindow& w = c->pn;
   w.node_off = c->node_off.p;
   w.scan_tmp = c->scan_tmp.p;
-  if ((rc = pn_records_enqueue(c, w, c->offsets.p, c->times.p, int64_t(c->times.cap), t0, R, N, K, B, nnz, st)))
+  if ((rc = pn_records_enqueue(c, w, c->rs.offsets.p, c->times.p, int64_t(c->times.cap), t0, R, N, K, B, nnz, st)))
     return rc;
   (void)hipEventRecord(c->pev[2], st);
   // the writer reads the total on the device and does nothing if it exceeds
@@ -812,9 +812,7 @@ void pn_check_set(cg_ctx* c, PnAsyncSet& a) {
   const unsigned long long stuck = static_cast<unsigned long long>(a.rm.res_host[1]);
   if (stuck != ~0ULL) {
     c->pa_rc = CG_ERANGE;
-    c->pa_msg = "rule " + std::to_string(stuck) +
-                ": the reference Next loop never terminates inside this horizon "
-                "(Next does not return, or returns a time <= its input and cycles)";
+    c->pa_msg = stuck_msg(stuck);
   } else if (E > a.rm_cap) {
     c->pa_rc = CG_ECAPACITY;
     c->pa_msg = "per-node async window (" + std::to_string(a.t0) + ", " + std::to_string(a.t1) + "]: " +
@@ -843,10 +841,6 @@ int pn_ensure_async(cg_ctx* c) {
     HIPCHK(hipEventCreateWithFlags(&a.written, hipEventDisableTiming));
     HIPCHK(hipEventCreateWithFlags(&a.nw0, hipEventDisableSystemFence));
     HIPCHK(hipEventCreateWithFlags(&a.nw1, hipEventDisableSystemFence));
-    HIPCHK(hipHostMalloc(reinterpret_cast<void**>(&a.rm.res_host), 16, hipHostMallocMapped | hipHostMallocCoherent));
-    HIPCHK(hipHostGetDevicePointer(reinterpret_cast<void**>(&a.rm.res_dev), a.rm.res_host, 0));
-    a.rm.res_host[0] = 0;
-    a.rm.res_host[1] = -1;
   }
   return CG_OK;
 }
@@ -907,27 +901,16 @@ int cg_expand_per_node_rules_device_async(cg_ctx* c, const cg_specs* s, const cg
   if (timed && t1 - t0 > 4096)
     return cg_fail(CG_EINVAL, "pipelined per-node windows in time order: windows of at most 4096 s");
   bool empty = false;
-  if ((rc = async_count_scan(c, a.rm, s, z, t0, t1, rm_cap, &empty))) return rc;
+  if ((rc = run_set_count_scan(a.rm, s, z, t0, t1, rm_cap, sc, nullptr, &empty))) return rc;
   if ((rc = a.times.ensure(std::max<int64_t>(rm_cap, 1))) || (rc = a.node_off.ensure(int64_t(N) + 1)) ||
       (rc = a.seg_tmp.ensure(scan_temp_bytes(std::max<int64_t>(NK, 1)))))
     return rc;
-  if (empty) {  // no rules: every list empty
-    a.rm.res_host[0] = 0;
-    a.rm.res_host[1] = -1;
-  } else {
-    const PlanArgs& pa = a.rm.pa;
-    const int64_t nruns = R * int64_t(pa.G);
-    // the whole persistent grid: beside the previous window's per-node writer
-    // only its free block slots run, and a smaller grid left this
-    // latency-bound writer with fewer waves (same-box A/B,
-    // profiles/r03_ab_pn_side.json: a quarter grid 3.21, a half 3.13, the
-    // whole 3.12 ms per pernode step)
-    launch_write_cf(s->d, pa, a.rm.run_anchor.p, a.rm.run_count.p, a.rm.run_dmask.p, a.rm.run_off.p, nruns,
-                    a.rm.block_run.p, rm_cap, a.times.p, c->write_blocks, sc);
-    if ((a.rm.plan.flags & (kPlanT0Walk | kPlanWalkSegs)) != 0)
-      launch_write_walk(s->d, R, pa, a.rm.run_anchor.p, a.rm.run_count.p, a.rm.run_dmask.p, a.rm.run_off.p, rm_cap,
-                        a.times.p, sc);
-  }
+  // (empty: no rules, every list empty.)  The whole persistent grid: beside
+  // the previous window's per-node writer only its free block slots run, and a
+  // smaller grid left this latency-bound writer with fewer waves (same-box
+  // A/B, profiles/r03_ab_pn_side.json: a quarter grid 3.21, a half 3.13, the
+  // whole 3.12 ms per pernode step)
+  if (!empty) run_set_write_enqueue(a.rm, s, rm_cap, a.times.p, c->write_blocks, sc);
   PnWindow& w = a.w;
   w.node_off = a.node_off.p;
   w.scan_tmp = a.seg_tmp.p;

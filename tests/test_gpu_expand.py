@@ -410,3 +410,94 @@ def test_async_result_hygiene():
     assert e2.expand_wait() == E2
     sp.free()
     e2.close()
+
+
+_CHAIN_ORACLE = {}
+
+
+def _chain_oracle(arr, zone, t0, t1):
+    """the oracle's CSR of the run-set test's rules (shared by its two cases)"""
+    key = (zone, t0, t1)
+    if key not in _CHAIN_ORACLE:
+        _CHAIN_ORACLE[key] = O.expand_batch(arr, t0, t1, oracle_zone(zone), threads=8)
+    return _CHAIN_ORACLE[key]
+
+
+@pytest.mark.parametrize("overlap", [True, False], ids=["overlap", "one-stream"])
+def test_run_sets_keep_their_own_state(overlap):
+    """Every consumer of the run-set chain in turn on one fresh context:
+    synchronous expansions, Next / lockTtl batches between two identical ones
+    (the plan-cache hit they cannot disturb), cg_count, pipelined calls that
+    come back to a set with a cached plan, and the never-ending reference loop
+    (Pacific/Apia over the skipped 2011-12-30) synchronously and pipelined with
+    ordinary calls right behind it -- no stale plan, unarmed stuck word or
+    stale R / capacity leaks from one call into the next: every readable
+    result is bit-exact against the oracle."""
+    from cronsun_amd.engine import Engine
+    from cronsun_amd._lib import check, lib
+    rng = np.random.default_rng(31)
+    scheds = [cron.Parse(s) for s in ["0 0 12 * * *", "0 0 9 * * Sat", "@daily"]]
+    scheds += [cron.Parse(random_spec(rng)) for _ in range(300)]
+    n = len(scheds)
+    arr = O.sched_array([to_oracle_sched(s.to_c()) for s in scheds])
+    e = Engine(0)
+    e.set_async_overlap(overlap)
+    sp = e.upload(scheds)
+
+    def same(got, zone, t0, t1):
+        eo, et = _chain_oracle(arr, zone, t0, t1)
+        assert np.array_equal(got[0], eo), (zone, t0, t1)
+        assert np.array_equal(got[1], et), (zone, t0, t1)
+
+    def waited():
+        E = e.expand_wait()
+        off = np.empty(n + 1, dtype=np.int64)
+        check(lib().cg_result_copy_offsets(e._h, off.ctypes.data))
+        return off, e.copy_times(0, E)
+
+    # 1-3: a synchronous expansion, Next and lockTtl in other zones, the same expansion again
+    ny, t0 = product_zone("America/New_York"), 1772953200 - 30 * 3600
+    first = e.expand(sp, ny, t0, t0 + 2 * DAY)
+    same(first, "America/New_York", t0, t0 + 2 * DAY)
+    nxt = e.next_batch(sp, product_zone("Australia/Lord_Howe"), np.full(n, t0, dtype=np.int64))
+    lh = oracle_zone("Australia/Lord_Howe")
+    assert [int(x) for x in nxt] == [O.sched_next(arr[i], t0, lh) for i in range(n)]
+    ttl = e.lock_ttl_batch(sp, product_zone("Pacific/Apia"), t0, 0, 0)
+    apia_o = oracle_zone("Pacific/Apia")
+    assert [int(x) for x in ttl] == [O.lock_ttl(arr[i], t0, apia_o, 0, 0, 300) for i in range(n)]
+    again = e.expand(sp, ny, t0, t0 + 2 * DAY)
+    assert np.array_equal(first[0], again[0]) and np.array_equal(first[1], again[1])
+    # 4: a count over another window
+    eo, _ = _chain_oracle(arr, "America/New_York", t0 + 7 * 3600, t0 + 7 * 3600 + DAY)
+    assert np.array_equal(e.count(sp, ny, t0 + 7 * 3600, t0 + 7 * 3600 + DAY), np.diff(eo))
+    # 5: five pipelined windows in a third zone, then the first of them again
+    dub = product_zone("Europe/Dublin")
+    wins = [(t0 + 5 * 3600 * i, t0 + 5 * 3600 * i + DAY) for i in range(5)]
+    for a, b in wins + wins[:1]:
+        e.expand_async(sp, dub, a, b)
+    got = waited()
+    a, b = wins[0]
+    sync = e.expand(sp, dub, a, b)
+    assert np.array_equal(got[0], sync[0]) and np.array_equal(got[1], sync[1])
+    same(got, "Europe/Dublin", a, b)
+    # 6, 7: the never-ending loop synchronously, an ordinary call right behind it
+    apia, ts = product_zone("Pacific/Apia"), 1325030400
+    assert O.stuck_rules(arr, ts, ts + 5 * DAY, apia_o)[0] == 1  # the Saturday rule
+    with pytest.raises(_lib.CgError) as err:
+        e.expand(sp, apia, ts, ts + 5 * DAY)
+    assert err.value.code == _lib.CG_ERANGE and "rule 1:" in err.value.msg
+    a = t0 + 11 * 3600
+    same(e.expand(sp, dub, a, a + 2 * DAY), "Europe/Dublin", a, a + 2 * DAY)
+    # 8: the same window pipelined, between two ordinary calls
+    e.expand_async(sp, dub, *wins[1])
+    e.expand_async(sp, apia, ts, ts + 5 * DAY)
+    e.expand_async(sp, dub, *wins[2])
+    with pytest.raises(_lib.CgError) as err:
+        e.expand_wait()
+    assert err.value.code == _lib.CG_ERANGE and "rule 1:" in err.value.msg
+    # 9: three ordinary pipelined calls
+    for a, b in wins[2:]:
+        e.expand_async(sp, dub, a, b)
+    same(waited(), "Europe/Dublin", *wins[4])
+    sp.free()
+    e.close()
