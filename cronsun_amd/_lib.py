@@ -143,6 +143,8 @@ def _declare(L):
         "cg_dispatcher_remove": ([vp, vp, sz], C.c_int),
         "cg_dispatcher_snapshot": ([vp, vp, vp, vp], C.c_int),
         "cg_dispatcher_bind_rules": ([vp, vp, C.c_int], C.c_int),
+        "cg_dispatcher_patch_rules": ([vp, vp, vp], C.c_int),
+        "cg_dispatcher_patch_times": ([vp, vp, C.c_int], C.c_int),
         "cg_dispatcher_fanout": ([vp, P(i64)], C.c_int),
         "cg_dispatcher_fanout_copy": ([vp, vp, vp, i64], C.c_int),
         "cg_dispatcher_fanout_range": ([vp, i64, i64, vp], C.c_int),

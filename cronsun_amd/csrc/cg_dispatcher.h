@@ -13,6 +13,7 @@ struct DispatchFanout {
   int64_t R = 0;      // its rules: slot i < R is rule i
   int64_t nnz = 0;    // (rule, node) pairs of the join
   int path = CG_FANOUT_AUTO;
+  int mode = 0;       // the exclude mode it was bound with (patches join under it)
   // rule -> nodes CSR and its stable node-major transpose (rules ascending
   // within a node)
   DBuf<int64_t> rn_off, nt_off;
@@ -30,7 +31,28 @@ struct DispatchFanout {
   DBuf<int32_t> deg, key0, key1, val1, hist;
   DBuf<int64_t> deg_off, hist_off;
   DBuf<char> scan_tmp;
+  // cg_dispatcher_patch_rules: the spare join a patch is built into (swapped
+  // with the bound one on success, so the join's footprint is held twice),
+  // the per-slot patch index and keep bitmap over the new rule count, the
+  // new degrees, the patch in ascending slot order {patch rule, slot, degree}
+  // with its scan, the delta pairs (key0, p_val0) and the removed pairs
+  // (p_rkey, p_rval) sorted by node with their node offsets, and the phase
+  // events / times of the last patch
+  DBuf<int64_t> rn_off2, nt_off2;
+  DBuf<int32_t> rn_nodes2, nt_rule2;
+  DBuf<int32_t> p_idx, p_deg, p_ord, p_val0;
+  DBuf<unsigned long long> p_keep;
+  DBuf<int64_t> p_doff, p_dnode_off, p_rem_off;
+  DBuf<int32_t> p_rkey, p_rval;
+  static constexpr int kPatchPhases = 5;  // join, rule-major, delta sort, removed sort, merge
+  hipEvent_t p_ev[kPatchPhases + 1] = {};
+  float p_ms[kPatchPhases] = {0, 0, 0, 0, 0};
   void release() {
+    rn_off2.release(); nt_off2.release(); rn_nodes2.release(); nt_rule2.release();
+    p_idx.release(); p_deg.release(); p_ord.release(); p_val0.release(); p_keep.release();
+    p_doff.release(); p_dnode_off.release(); p_rem_off.release(); p_rkey.release(); p_rval.release();
+    for (hipEvent_t& e : p_ev)
+      if (e) (void)hipEventDestroy(e), e = nullptr;
     rn_off.release(); nt_off.release(); rn_nodes.release(); nt_rule.release();
     node_off.release(); slots.release(); tile_cnt.release(); tile_base.release();
     deg.release(); key0.release(); key1.release(); val1.release(); hist.release();

@@ -12,7 +12,11 @@ dispatcher (cg_dispatcher_*, Engine.dispatcher).
                             directly for deterministic drivers and tests
   ClusterCron(jobset)       every cronnode's Cron as one table: begin(now) /
                             wake(now) -> {node ID: [(Job.ID, Rule.ID), ...]}
-                            (cg_dispatcher_bind_rules + cg_dispatcher_fanout)
+                            (cg_dispatcher_bind_rules + cg_dispatcher_fanout);
+                            put_job / del_job / put_group / del_group(.., now)
+                            follow the watch stream (node/node.go:143-359)
+  ClusterState(jobset)      the live picture behind those edits, host only:
+                            a watch event -> an Edit (set / remove / patch)
 
 Entry state (schedule, Next, Prev) lives in HBM; a wake is one fused kernel
 plus an ordered compaction instead of sort.Sort over every entry.  Jobs run on
@@ -22,7 +26,7 @@ cron.go:189-199).  Times are whole unix seconds (Next drops nanoseconds).
 import logging
 import threading
 import time
-from dataclasses import dataclass
+from dataclasses import dataclass, field
 from typing import Any, Dict, List, Optional
 
 import numpy as np
@@ -204,13 +208,188 @@ class Cron:
             self._thread = None
 
 
+@dataclass
+class Edit:
+    """What one watch event asks of the dispatcher (ClusterState.put_job /
+    del_job / put_group / del_group): timers to set, slots to remove, and the
+    rule patch (cg_dispatcher_patch_rules) that moves the node sets."""
+    set_slots: List[int] = field(default_factory=list)
+    set_schedules: List[Any] = field(default_factory=list)
+    remove_slots: List[int] = field(default_factory=list)
+    patch: Any = None                    # engine.RulesIn of whole jobs, or None
+    patch_slots: Any = None              # int64 [patch.n_rules]
+
+
+class ClusterState:
+    """The live picture behind a ClusterCron, on the host (no device needed):
+    jobs by ID with their slots, groups, the node-ID table and the
+    group -> jobs links (n.link, node/node.go:143-359).  Every watch event
+    becomes an Edit.  An edited cluster is the state every cronnode would be
+    in after a fresh loadJobs of the edited data, with per-slot Next / Prev
+    carried over.
+
+    Slots: the initial JobSet's rule i is slot i.  A new job, or a known job
+    whose Rule.ID sequence changed, takes fresh contiguous slots at the end,
+    so within a job slot order is always rule order and the cluster stays
+    expressible as one rule set with rule i = slot i (vacated slots: rules
+    without nodes).  self.jobs is kept in slot order."""
+
+    def __init__(self, jobset):
+        groups = getattr(jobset, "groups", None)
+        if groups is None:
+            raise TypeError("ClusterState needs a model.JobSet (jobs and groups by ID)")
+        self.groups = dict(groups)
+        self.jobs: Dict[str, Any] = {}
+        self.slots: Dict[str, List[int]] = {}
+        self.link: Dict[str, set] = {}      # Group.ID -> Job.IDs with a rule naming it
+        self.slot_cmd: List[Optional[tuple]] = []  # slot -> (Job.ID, Rule.ID), None when vacated
+        n_nodes = jobset.rules_in().n_nodes
+        self.node_ids: List[str] = [jobset.node_id(i) for i in range(n_nodes)]
+        self._node_index = {nid: i for i, nid in enumerate(self.node_ids)}
+        for j in jobset.jobs:
+            if j.ID in self.jobs:
+                raise ValueError(f"job {j.ID!r} appears twice")
+            self._add(j)
+
+    @property
+    def n_slots(self):
+        return len(self.slot_cmd)
+
+    def node_index(self, nid):
+        """The node's index in the cluster's table (appended when new)."""
+        i = self._node_index.get(nid)
+        if i is None:
+            i = self._node_index[nid] = len(self.node_ids)
+            self.node_ids.append(nid)
+        return i
+
+    def jobset(self):
+        """A fresh JobSet of the current jobs (slot order) and groups."""
+        from .model import JobSet
+        return JobSet(list(self.jobs.values()), self.groups)
+
+    # ---------------------------------------------------------- bookkeeping
+    def _add(self, job):
+        first = len(self.slot_cmd)
+        self.jobs[job.ID] = job
+        self.slots[job.ID] = list(range(first, first + len(job.Rules)))
+        self.slot_cmd.extend((job.ID, r.ID) for r in job.Rules)
+        self._link(job)
+        return self.slots[job.ID]
+
+    def _link(self, job):
+        for r in job.Rules:
+            for gid in r.GroupIDs:
+                self.link.setdefault(gid, set()).add(job.ID)
+
+    def _unlink(self, job):
+        for r in job.Rules:
+            for gid in r.GroupIDs:
+                ids = self.link.get(gid)
+                if ids is not None:
+                    ids.discard(job.ID)
+                    if not ids:
+                        del self.link[gid]
+
+    def _drop(self, jid):
+        """Forget a job; returns a rule-less stand-in that vacates its slots."""
+        from .model import Job, JobRule
+        old, slots = self.jobs.pop(jid), self.slots.pop(jid)
+        self._unlink(old)
+        for s in slots:
+            self.slot_cmd[s] = None
+        return Job(jid, Rules=[JobRule(r.ID) for r in old.Rules]), slots
+
+    def _patch(self, edit, parts):
+        """parts: [(job, slots)] -> the patch of those whole jobs.  A small
+        JobSet of the jobs and the groups they reference (an absent group
+        stays referenced but missing), node indices remapped by node ID to the
+        cluster's table."""
+        from .engine import RulesIn
+        from .model import JobSet
+        parts = [(j, sl) for j, sl in parts if sl]
+        if not parts:
+            return edit
+        gids = {g for j, _ in parts for r in j.Rules for g in r.GroupIDs}
+        small = JobSet([j for j, _ in parts], {g: self.groups[g] for g in sorted(gids) if g in self.groups})
+        rin = small.rules_in()
+        remap = np.array([self.node_index(small.node_id(i)) for i in range(rin.n_nodes)], dtype=np.int32)
+        R, G = rin.n_rules, rin.n_groups
+        arrays = {f: getattr(rin, f) for f in RulesIn.FIELDS}
+        for vals, n in (("nids", rin.nid_off[R]), ("ex", rin.ex_off[R]),
+                        ("group_nodes", rin.group_off[G] if G else 0)):
+            arrays[vals] = remap[arrays[vals][:int(n)]] if n else np.zeros(0, np.int32)
+        edit.patch = RulesIn(len(self.node_ids), G, R, rin.n_jobs, rule_key=rin.rule_key[:R]
+                             if rin.rule_key is not None else None, **arrays)
+        edit.patch_slots = np.array([s for _, sl in parts for s in sl], dtype=np.int64)
+        return edit
+
+    # --------------------------------------------------------------- events
+    def put_job(self, job):
+        """A job put (addJob / modJob, node/node.go:143-238)."""
+        job.ValidRules()
+        e = Edit()
+        old = self.jobs.get(job.ID)
+        if old is not None and [r.ID for r in old.Rules] == [r.ID for r in job.Rules]:
+            # the same Cmds: slots reused, a timer rescheduled only when its
+            # string changed (modCmd, node/node.go:226-233)
+            slots = self.slots[job.ID]
+            for s, ro, rn in zip(slots, old.Rules, job.Rules):
+                if ro.Timer != rn.Timer:
+                    e.set_slots.append(s)
+                    e.set_schedules.append(rn.Schedule)
+            self._unlink(old)
+            self.jobs[job.ID] = job
+            self._link(job)
+            return self._patch(e, [(job, slots)])
+        parts = []
+        if old is not None:  # other Cmds: delJob, then addJob at the end
+            gone, gone_slots = self._drop(job.ID)
+            e.remove_slots = list(gone_slots)
+            parts.append((gone, gone_slots))
+        slots = self._add(job)
+        e.set_slots = list(slots)
+        e.set_schedules = [r.Schedule for r in job.Rules]
+        parts.append((job, slots))
+        return self._patch(e, parts)
+
+    def del_job(self, jid):
+        """A job delete (delJob, node/node.go:176-189)."""
+        e = Edit()
+        if jid not in self.jobs:
+            return e
+        gone, slots = self._drop(jid)
+        e.remove_slots = list(slots)
+        return self._patch(e, [(gone, slots)])
+
+    def _group_changed(self, gid):
+        ids = self.link.get(gid, ())
+        return self._patch(Edit(), [(j, self.slots[j.ID]) for j in self.jobs.values() if j.ID in ids])
+
+    def put_group(self, group):
+        """A group put (addGroup / modGroup, node/node.go:240-318): every job
+        with a rule naming it is patched, no timer moves."""
+        self.groups[group.ID] = group
+        return self._group_changed(group.ID)
+
+    def del_group(self, gid):
+        """A group delete: its jobs are patched with the group missing."""
+        if self.groups.pop(gid, None) is None:
+            return Edit()
+        return self._group_changed(gid)
+
+
 class ClusterCron:
     """Every cronnode's Cron at once: one dispatcher table over all rules of
     a model.JobSet (slot i = rule i), fanned out to nodes after each wake.
     A cronnode runs its own Cron over Job.Cmds(node, groups)
     (node/node.go:121-158); wake(now) returns what each of those run loops
     fires at that instant.  No thread: the deterministic driver, like
-    Cron.begin / Cron.wake."""
+    Cron.begin / Cron.wake.
+
+    put_job / del_job / put_group / del_group follow the watch stream
+    (node/node.go:143-359) through ClusterState: timers by Dispatcher.set /
+    remove, node sets by Dispatcher.patch_rules -- no rebind."""
 
     def __init__(self, jobset, location=None, mode=EXCLUDE_NONE, engine=None):
         self.jobset = jobset
@@ -219,18 +398,28 @@ class ClusterCron:
         self._engine = engine
         self._d = None
         self._rules = None
+        self.state = None
+
+    def _resolve_engine(self):
+        from .engine import default_engine
+        self._engine = self._engine or default_engine()
+        return self._engine
 
     def begin(self, now):
         """Upload the set's schedules and rules, start the table at `now`
         (cron.go:212-215) and bind the rule -> node join."""
-        from .engine import default_engine
-        self._engine = self._engine or default_engine()
+        eng = self._resolve_engine()
         js = self.jobset
-        self._rules = self._engine.upload_rules(js.rules_in())
-        self._d = self._engine.dispatcher(js.schedules(), self._loc, now)
+        self._rules = eng.upload_rules(js.rules_in())
+        self._d = eng.dispatcher(js.schedules(), self._loc, now)
         self._d.bind_rules(self._rules, self._mode)
         self._node_ids = {}
         self._cmd = [(js.jobs[j].ID, r.ID) for j, r in zip(js.rule_job, js.rules)]
+        # the live picture the edits work on (a jobset without groups by ID
+        # cannot be edited)
+        self.state = ClusterState(js) if getattr(js, "groups", None) is not None else None
+        if self.state is not None:
+            self._cmd = self.state.slot_cmd
 
     @property
     def effective(self):
@@ -238,19 +427,61 @@ class ClusterCron:
 
     def wake(self, now):
         """The timer fired at `now`: {node ID: [(Job.ID, Rule.ID), ...]} of the
-        nodes with something due, each node's Cmds in job order, then rule
-        order."""
+        nodes with something due, each node's Cmds in ascending slot order:
+        job order, then rule order, where a job put with other Rule.IDs (or a
+        new job) comes after every job that was there before it."""
         if self._d.effective == ZERO_TIME or now < self._d.effective:
             return {}
         self._d.fire_count(now)
         node_off, slots = self._d.fanout()
         out = {}
         for n in np.flatnonzero(np.diff(node_off)):
-            nid = self._node_ids.get(int(n))
-            if nid is None:
-                nid = self._node_ids[int(n)] = self.jobset.node_id(int(n))
-            out[nid] = [self._cmd[int(s)] for s in slots[node_off[n]:node_off[n + 1]]]
+            out[self._node_id(int(n))] = [self._cmd[int(s)] for s in slots[node_off[n]:node_off[n + 1]]]
         return out
+
+    def _node_id(self, n):
+        if self.state is not None:
+            return self.state.node_ids[n]
+        nid = self._node_ids.get(n)
+        if nid is None:
+            nid = self._node_ids[n] = self.jobset.node_id(n)
+        return nid
+
+    # ---------------------------------------------------------------- edits
+    def _editable(self):
+        self._resolve_engine()  # CG_ENODEV without a device
+        if self._d is None:
+            raise RuntimeError("ClusterCron: begin(now) comes before the first edit")
+        if self.state is None:
+            raise TypeError("ClusterCron: edits need a model.JobSet (jobs and groups by ID)")
+        return self.state
+
+    def apply(self, edit, now):
+        """One Edit: timers first (the table grows as Dispatcher.set allows),
+        then the patch is uploaded, applied and freed."""
+        if edit.remove_slots:
+            self._d.remove(edit.remove_slots)
+        if edit.set_slots:
+            self._d.set(edit.set_slots, edit.set_schedules, now)
+        if edit.patch is not None:
+            dr = self._engine.upload_rules(edit.patch)
+            try:
+                self._d.patch_rules(dr, edit.patch_slots)
+            finally:
+                dr.free()
+        return edit
+
+    def put_job(self, job, now):
+        return self.apply(self._editable().put_job(job), now)
+
+    def del_job(self, jid, now):
+        return self.apply(self._editable().del_job(jid), now)
+
+    def put_group(self, group, now):
+        return self.apply(self._editable().put_group(group), now)
+
+    def del_group(self, gid, now):
+        return self.apply(self._editable().del_group(gid), now)
 
     def close(self):
         if self._d is not None:
@@ -271,4 +502,4 @@ def NewWithLocation(location):
     return Cron(location)
 
 
-__all__ = ["ClusterCron", "Cron", "Entry", "FuncJob", "New", "NewWithLocation"]
+__all__ = ["ClusterCron", "ClusterState", "Cron", "Edit", "Entry", "FuncJob", "New", "NewWithLocation"]

@@ -173,10 +173,32 @@ class Dispatcher:
     # ------------------------------------------------------ node fan-out
     def bind_rules(self, drules, mode=_lib.EXCLUDE_NONE):
         """Slot i is rule i of the uploaded rule set `drules`: builds the
-        rule -> node join the fan-out of a wake uses (bind again after an edit
-        of groups or rules)."""
+        rule -> node join the fan-out of a wake uses (an edit of single jobs
+        or groups: patch_rules)."""
         check(lib().cg_dispatcher_bind_rules(self._h, drules._h, int(mode)))
         self._n_nodes = drules.n_nodes
+
+    def patch_rules(self, drules, slots):
+        """Rule p of the uploaded patch `drules` is slot slots[p]: that slot's
+        node set becomes what the join gives rule p inside the patch (under
+        the mode of bind_rules); every other slot keeps its own.  The patch
+        holds every rule of each affected job, in the job's order, with the
+        bound set's node and group numbering; slots may lie past the bound
+        rule count (after set) and the patch may bring new nodes.  The last
+        wake stays valid: fanout() gives it again under the new join."""
+        sl = np.ascontiguousarray(np.atleast_1d(slots), dtype=np.int64)
+        if sl.shape != (drules.n_rules,):
+            raise ValueError("patch_rules: one slot per patch rule")
+        check(lib().cg_dispatcher_patch_rules(self._h, drules._h, sl.ctypes.data))
+        if drules.n_rules:
+            self._n_nodes = max(getattr(self, "_n_nodes", 0), drules.n_nodes)
+
+    def patch_ms(self):
+        """Device ms of the last patch_rules by phase: the patch's join,
+        rule-major rows, delta pairs + sort, removed pairs + sort, merge."""
+        buf = (C.c_float * 5)()
+        n = check(lib().cg_dispatcher_patch_times(self._h, buf, 5))
+        return list(buf)[:n]
 
     def set_fanout_path(self, path):
         """CG_FANOUT_AUTO (default) / _FILTER / _DUE: force a device path

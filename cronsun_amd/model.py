@@ -147,6 +147,7 @@ class JobSet(_Interned):
         check(L.cg_jobset_new(C.byref(h)))
         self._h = h
         self.jobs = list(jobs)
+        self.groups: GroupMap = dict(groups)
         self.rules: List[JobRule] = []
         self.rule_job: List[int] = []
         for gid, g in groups.items():

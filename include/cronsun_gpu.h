@@ -548,17 +548,63 @@ int cg_expand_per_node_wait(cg_ctx* ctx, int64_t* n_events, int64_t* n_events_al
  *                             bad, d has fewer slots than the set has rules,
  *                             or pipelined per-node windows / rule-major
  *                             calls are pending on the ctx.  Binding again
- *                             rebuilds the join (after an edit of groups or
- *                             rules).  The ctx's per-node transpose cache is
+ *                             rebuilds the join from scratch; an edit of single
+ *                             jobs or groups is cheaper as a patch (below).
+ *                             The ctx's per-node transpose cache is
  *                             dropped: the next per-node call rebuilds its own.
+ *   cg_dispatcher_patch_rules  follows the watch stream (addJob / modJob /
+ *                             delJob / modGroup, node/node.go:143-359) without
+ *                             a rebind: rule p of `patch` is slot slot[p] of d,
+ *                             and after the call that slot's node set is what
+ *                             the join gives rule p inside `patch`, under the
+ *                             exclude mode d was bound with.  Every slot not
+ *                             named keeps its node set.  The Cmd-key
+ *                             last-writer rule and the cumulative excludes act
+ *                             within a job, so `patch` must hold EVERY rule of
+ *                             each affected job, in the job's order, with the
+ *                             node and group numbering of the bound set
+ *                             (groups the patch does not reference may be left
+ *                             out as missing).  slot[p] may be >= the bound
+ *                             rule count, up to cg_dispatcher_count(d) - 1:
+ *                             the bound rule count becomes max slot + 1 and
+ *                             slots skipped in between have no nodes.  `patch`
+ *                             may have more nodes than the bound set: new
+ *                             nodes start with empty rows.  A rule with empty
+ *                             lists, or of a paused job, gives its slot the
+ *                             empty set (how a deleted job's slots are
+ *                             vacated).  Afterwards the join is element for
+ *                             element what cg_dispatcher_bind_rules builds
+ *                             from the whole edited rule set (rule i = slot
+ *                             i); the result is deterministic.  The last wake
+ *                             stays valid: only its fan-out is dropped, and
+ *                             cg_dispatcher_fanout may be called again for it
+ *                             under the new join.  The new join is built into
+ *                             spare buffers and swapped in at the end: on any
+ *                             error the bound join is what it was, and a
+ *                             dispatcher that has been patched holds the
+ *                             join's memory twice (grow-only, released with
+ *                             d).  A patch of zero rules changes nothing.
+ *                             CG_EINVAL when d is unbound, `patch` is on
+ *                             another ctx, a slot is < 0 or >= the
+ *                             dispatcher's count, a slot appears twice, or
+ *                             pipelined calls are pending (as for bind).  The
+ *                             ctx's per-node transpose cache is dropped, as by
+ *                             a bind.  Cost: one streaming pass over the join
+ *                             (about 16 B per pair) plus a sort of the
+ *                             patch's own pairs.
+ *   cg_dispatcher_patch_times  ms of the last patch's device phases: [0] the
+ *                             patch's join, [1] rule-major rows, [2] delta
+ *                             pairs + sort, [3] removed pairs + sort, [4] merge;
+ *                             returns the entries written (at most 5).
  *   cg_dispatcher_fanout      fans out the last cg_dispatcher_fire's due list;
  *                             *n_pairs = (node, slot) pairs.  The result (and
  *                             the due list) is valid until the next call on
  *                             d.  A slot >= n_rules (added by
  *                             cg_dispatcher_set past the bound set) has no
- *                             nodes; a replaced slot < n_rules keeps its node
- *                             set (modCmd changes only the timer,
- *                             node/node.go:219-238).  CG_EINVAL when d is
+ *                             nodes until a patch names it; a replaced slot
+ *                             < n_rules keeps its node set (modCmd changes
+ *                             only the timer, node/node.go:219-238).
+ *                             CG_EINVAL when d is
  *                             unbound or no wake was made since the last
  *                             set / remove.
  *   cg_dispatcher_fanout_copy node_off [N+1] and the slots to the host
@@ -576,6 +622,9 @@ int cg_expand_per_node_wait(cg_ctx* ctx, int64_t* n_events, int64_t* n_events_al
 #define CG_FANOUT_FILTER 1 /* stream the transpose, test each rule's due bit */
 #define CG_FANOUT_DUE 2    /* expand the due slots' node lists, sort by node */
 int cg_dispatcher_bind_rules(cg_dispatcher* d, const cg_rules* rules, int mode);
+int cg_dispatcher_patch_rules(cg_dispatcher* d, const cg_rules* patch,
+                              const int64_t* slot /* [patch n_rules] */);
+int cg_dispatcher_patch_times(const cg_dispatcher* d, float* ms, int n);
 int cg_dispatcher_fanout(cg_dispatcher* d, int64_t* n_pairs);
 int cg_dispatcher_fanout_copy(const cg_dispatcher* d, int64_t* node_off /* [N+1] */, int32_t* slots,
                               int64_t cap);

@@ -524,8 +524,8 @@ const (
 
 // BindRules makes slot i of the dispatcher rule i of the jobset: one table for
 // every cronnode's Cron (node/node.go:121-158).  It uploads the jobset's rules
-// and builds the rule -> node join Fanout uses; call it again after an edit of
-// groups or rules.
+// and builds the rule -> node join Fanout uses; an edit of single jobs or
+// groups is cheaper as a PatchRules.
 func (d *Dispatcher) BindRules(j *Jobset, mode int) error {
 	defer runtime.KeepAlive(d)
 	defer runtime.KeepAlive(j)
@@ -542,6 +542,42 @@ func (d *Dispatcher) BindRules(j *Jobset, mode int) error {
 		return lastErr(rc)
 	}
 	d.nodes = int(rin.n_nodes)
+	return nil
+}
+
+// PatchRules follows the watch stream (addJob / modJob / delJob / modGroup,
+// node/node.go:143-359) without a rebind: rule p of the patch jobset is slot
+// slots[p], and afterwards that slot runs on the nodes the patch gives rule p;
+// every other slot keeps its nodes.  The patch holds every rule of each
+// affected job, in the job's order, and numbers nodes as the bound jobset does
+// (intern the cluster's node IDs first, in order, e.g. as the NodeIDs of a
+// group no rule names; new node IDs go behind them).  Slots may lie past the
+// bound rule count (after Set), a rule without nodes vacates its slot, and the
+// last Fire stays valid: Fanout may be called again for it.
+func (d *Dispatcher) PatchRules(j *Jobset, slots []int64) error {
+	defer runtime.KeepAlive(d)
+	defer runtime.KeepAlive(j)
+	var rin C.cg_rules_in
+	if rc := C.cg_jobset_rules(j.js, &rin); rc != 0 {
+		return lastErr(rc)
+	}
+	if len(slots) != int(rin.n_rules) {
+		return fmt.Errorf("gpu: PatchRules: %d slots for %d rules", len(slots), int(rin.n_rules))
+	}
+	if len(slots) == 0 {
+		return nil
+	}
+	var r *C.cg_rules
+	if rc := C.cg_rules_upload(d.e.ctx, &rin, &r); rc != 0 {
+		return lastErr(rc)
+	}
+	defer C.cg_rules_free(r) // the patch's rows are copied into the dispatcher
+	if rc := C.cg_dispatcher_patch_rules(d.d, r, (*C.int64_t)(unsafe.Pointer(&slots[0]))); rc != 0 {
+		return lastErr(rc)
+	}
+	if n := int(rin.n_nodes); n > d.nodes {
+		d.nodes = n
+	}
 	return nil
 }
 
