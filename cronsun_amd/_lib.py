@@ -182,6 +182,12 @@ def _declare(L):
         "cg_rules_free": ([vp], None),
         "cg_expand_per_node_rules_device": ([vp, vp, vp, i64, i64, vp, C.c_int, P(i64), P(i64)],
                                             C.c_int),
+        "cg_profile_device": ([vp, vp, vp, i64, i64, i32], C.c_int),
+        "cg_profile_per_node_device": ([vp, vp, vp, i64, i64, i32, vp, C.c_int], C.c_int),
+        "cg_profile_result_device": ([vp, P(vp), P(vp), P(vp), P(i64), P(i32), P(i32)], C.c_int),
+        "cg_profile_copy_rules": ([vp, i64, i64, vp], C.c_int),
+        "cg_profile_copy_totals": ([vp, vp], C.c_int),
+        "cg_profile_copy_nodes": ([vp, i32, i32, vp], C.c_int),
         "cg_rule_nodes": ([vp, P(cg_rules_in), C.c_int, vp, vp, i64, P(i64)], C.c_int),
         "cg_comm_unique_id": ([vp], C.c_int),
         "cg_comm_init": ([vp, C.c_int, C.c_int, vp, P(vp)], C.c_int),

@@ -243,8 +243,10 @@ struct cg_ctx {
   // offsets, k_node_write) of the last per-node call, [9..11] dispatcher
   // wake (scan, due compaction, advance) of the last cg_dispatcher_fire, [12]
   // the time-order pass of the last cg_node_result_order_by_time, [13] the
-  // last cg_dispatcher_fanout
-  float kt[14] = {0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0};
+  // last cg_dispatcher_fanout, [14..18] the last profile call (k_profile_rules,
+  // k_profile_walk, k_profile_totals, join + transpose when rebuilt, the
+  // node matrix)
+  float kt[19] = {0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0};
   // expansion phase timing: 2 = an event between every phase (kt[0..5]);
   // 1 = events around k_write_cf only (kt[3]; the others read -1).  Each
   // event recorded between two kernels costs 6-12 us of idle GPU on this
@@ -354,6 +356,17 @@ struct cg_ctx {
   hipStream_t st_ot = nullptr;
   hipEvent_t ot_fork = nullptr, ot_join = nullptr;
 
+  // fire profile (cg_profile.hip): the matrices of the last profile call --
+  // rule counts [pf_R][pf_B], bucket totals [pf_B], node counts [pf_N][pf_B]
+  // (pf_has_nodes) -- in buffers no other entry point touches; the chunk
+  // counts / offsets of the nodes' rule lists and the heavy nodes' partials
+  DBuf<int32_t> pf_rules, pf_chunk_cnt;
+  DBuf<int64_t> pf_totals, pf_nodes, pf_part, pf_chunk_off;
+  int64_t pf_R = 0;
+  int32_t pf_N = 0, pf_B = 0;
+  bool pf_valid = false, pf_has_nodes = false;
+  hipEvent_t pfev[6] = {};  // created by the first profile call
+
   void free_all() {
     for (AsyncSet& a : as) a.release();
     for (PnAsyncSet& a : pns) a.release();
@@ -383,6 +396,10 @@ struct cg_ctx {
     ts_start.release(); ts_hi.release();
     ts_base.release(); ts_off.release(); node_time2.release(); ts_node_off.release();
     mr_rb.release(); mr_tp.release(); mr_t.release(); mr_r.release();
+    pf_rules.release(); pf_chunk_cnt.release(); pf_totals.release(); pf_nodes.release();
+    pf_part.release(); pf_chunk_off.release();
+    for (hipEvent_t& e : pfev)
+      if (e) (void)hipEventDestroy(e), e = nullptr;
   }
 };
 
@@ -426,6 +443,12 @@ int plan_args(const cg::Plan& plan, const PlanLayout& L, char* dev_base, int64_t
 // made sure that nothing enqueued earlier still reads or writes rs.
 int run_set_count_scan(RunSet& rs, const cg_specs* s, const cg_zone* z, int64_t t0, int64_t t1, int64_t map_cap,
                        hipStream_t st, hipEvent_t* ev, bool* empty);
+// What a synchronous call does before its count and scan on the ctx stream
+// into c->rs (cg_expand.cpp): drains and discards pending pipelined calls,
+// clears the readable rule-major result, checks the horizon; an empty call's
+// offsets are zeroed and the stream drained.  c->mu held.
+int sync_count_scan(cg_ctx* c, const cg_specs* s, const cg_zone* z, int64_t t0, int64_t t1, bool* empty,
+                    int64_t map_cap = 0);
 // the writers of the runs counted last into out (cap events: the capacity the
 // slice map was built for), on st: k_write_cf on `blocks` blocks, after_cf (or
 // null) recorded behind it, then k_write_walk when the plan has walked runs

@@ -95,8 +95,8 @@ std::string stuck_msg(unsigned long long rule) {
 // ------------------------------------------------------- synchronous calls
 // What a synchronous call does before its count and scan on the ctx stream
 // into c->rs; an empty call's offsets are zeroed and the stream drained.
-static int sync_count_scan(cg_ctx* c, const cg_specs* s, const cg_zone* z, int64_t t0, int64_t t1,
-                           bool* empty, int64_t map_cap = 0) {
+int sync_count_scan(cg_ctx* c, const cg_specs* s, const cg_zone* z, int64_t t0, int64_t t1, bool* empty,
+                    int64_t map_cap) {
   // no readable result until this call succeeds (the accessors check last_R/E).
   // Asynchronous calls still pending are drained and their results and errors
   // discarded: this call's result replaces them (cronsun_gpu.h).

@@ -1,0 +1,409 @@
+// cg_profile.hip -- fire profile: fires per (rule, bucket) and per (node,
+// bucket) over B fixed-width buckets of (t0, t0 + B*w], computed from the run
+// records of the count chain and the cached rule->node transpose; no fire
+// list is written ("load profile").
+//
+//   k_profile_rules   one lane per cell of the rule matrix [R][B], lanes along
+//                     buckets: the closed-form runs' fires per bucket
+//                     (cg_profile.h, profile_cell); every cell stored once
+//   k_profile_walk    one lane per rule: the walked runs' fires, stepped by
+//                     next_exact and added to the rule's own row
+//   k_profile_totals  column sums of the rule matrix (int64 [B])
+//   k_profile_nodes   node matrix [N][B] = transpose x rule matrix (integer
+//                     SpMM): per (chunk of a node's rule list, 64-bucket tile)
+//   k_profile_nodes_reduce  sums the chunk partials of nodes whose list spans
+//                     more than one chunk
+#include <hip/hip_runtime.h>
+
+#include <algorithm>
+#include <mutex>
+#include <string>
+
+#include "../../include/cronsun_gpu.h"
+#include "cg_api_internal.h"
+#include "cg_profile.h"
+#include "cg_stage.h"
+
+using namespace cg;
+
+namespace {
+
+constexpr int kMaxBuckets = 4096;
+// rules of a node's list (k_profile_nodes) / rows of the rule matrix
+// (k_profile_totals) summed by one block per bucket tile
+constexpr int kNodeChunk = 512;
+constexpr int kTotalChunk = 4096;
+
+// ------------------------------------------------------------ rule matrix --
+__global__ __launch_bounds__(256) void k_profile_rules(const DSpec* __restrict__ specs, int64_t R, PlanArgs p,
+                                                        const int64_t* __restrict__ run_anchor,
+                                                        const int32_t* __restrict__ run_count,
+                                                        const uint32_t* __restrict__ run_dmask, int64_t w, int32_t B,
+                                                        int32_t* __restrict__ out) {
+  extern __shared__ __align__(16) char lds[];
+  PlanView v = stage_plan(p, lds);
+  const int G = p.G;
+  const int64_t cells = R * B, stride = int64_t(gridDim.x) * blockDim.x;
+  int64_t i = blockIdx.x * int64_t(blockDim.x) + threadIdx.x;
+  if (i >= cells) return;
+  // cell i = (rule r, bucket b), advanced without a division per cell
+  const int64_t dr = stride / B;
+  const int32_t db = int32_t(stride - dr * B);
+  int64_t r = i / B;
+  int32_t b = int32_t(i - r * B);
+  for (; i < cells; i += stride) {
+    const DSpec sp = load_spec(specs + r);
+    const CFRule c = cf_rule(sp);
+    const int64_t j0 = r * G;
+    const int64_t lo = p.t0 + int64_t(b) * w;
+    out[i] = profile_cell(sp, c, v.segs, G, run_anchor + j0, run_count + j0, run_dmask + j0, p.t1, lo, lo + w);
+    r += dr;
+    b += db;
+    if (b >= B) {
+      b -= B;
+      r++;
+    }
+  }
+}
+
+__global__ __launch_bounds__(256) void k_profile_walk(const DSpec* __restrict__ specs, int64_t R, PlanArgs p,
+                                                       const int64_t* __restrict__ run_anchor,
+                                                       const int32_t* __restrict__ run_count,
+                                                       const uint32_t* __restrict__ run_dmask, int64_t w, int32_t B,
+                                                       int32_t* __restrict__ out) {
+  extern __shared__ __align__(16) char lds[];
+  PlanView v = stage_plan(p, lds);
+  const int G = p.G;
+  for (int64_t r = blockIdx.x * int64_t(blockDim.x) + threadIdx.x; r < R; r += int64_t(gridDim.x) * blockDim.x) {
+    DSpec sp;
+    bool loaded = false;
+    int32_t* row = out + r * B;  // this lane's own row
+    for (int s = 0; s < G; s++) {
+      const int64_t j = r * G + s;
+      const int32_t n = run_count[j];
+      if (n == 0 || !run_is_walked(v.segs[s], run_dmask[j])) continue;
+      if (!loaded) {
+        sp = load_spec(specs + r);
+        loaded = true;
+      }
+      if (sp.kind == KIND_EVERY) break;  // closed form in every segment
+      int64_t t = run_anchor[j];
+      for (int32_t q = 0; q < n; q++) {
+        t = next_exact(sp, v.z, t, p.t1);
+        const int64_t b = (t - p.t0 - 1) / w;
+        if (t > p.t0 && b < B) row[b] += 1;
+      }
+    }
+  }
+}
+
+// ------------------------------------------------- column / node list sums --
+// A block sums rows of the rule matrix for one tile of up to 64 buckets,
+// lanes along buckets.  With B < 64 a wave holds 64 / B rows side by side, so
+// a block works on `slots` rows at a time: row slot, bucket col of a thread.
+struct TileLane {
+  int32_t W, slots, slot, col;
+  bool active;
+};
+__device__ __forceinline__ TileLane tile_lane(int32_t B) {
+  TileLane t;
+  t.W = B < 64 ? B : 64;
+  const int32_t k = 64 / t.W, lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
+  const int32_t sub = lane / t.W;
+  t.col = int32_t(blockIdx.y) * 64 + (lane - sub * t.W);
+  t.slots = 4 * k;
+  t.slot = wv * k + sub;
+  t.active = sub < k && t.col < B;
+  return t;
+}
+// sum of the block's per-thread partials per bucket, valid in threads < W
+__device__ __forceinline__ int64_t tile_reduce(const TileLane& t, int64_t acc) {
+  __shared__ int64_t sh[256];
+  sh[threadIdx.x] = t.active ? acc : 0;
+  __syncthreads();
+  int64_t sum = 0;
+  if (int32_t(threadIdx.x) < t.W) {
+    const int32_t k = t.slots / 4;
+    for (int wv = 0; wv < 4; wv++)
+      for (int s = 0; s < k; s++) sum += sh[wv * 64 + s * t.W + threadIdx.x];
+  }
+  return sum;
+}
+
+// tot [B] zeroed before the launch: one 64-bit atomic per block and column
+__global__ __launch_bounds__(256) void k_profile_totals(const int32_t* __restrict__ rc, int64_t R, int32_t B,
+                                                         unsigned long long* __restrict__ tot) {
+  const TileLane t = tile_lane(B);
+  const int64_t beg = int64_t(blockIdx.x) * kTotalChunk, end = beg + kTotalChunk < R ? beg + kTotalChunk : R;
+  int64_t acc = 0;
+  if (t.active) {
+#pragma unroll 4
+    for (int64_t r = beg + t.slot; r < end; r += t.slots) acc += rc[r * B + t.col];
+  }
+  const int64_t sum = tile_reduce(t, acc);
+  if (int32_t(threadIdx.x) < t.W && t.col < B && sum != 0) atomicAdd(tot + t.col, (unsigned long long)sum);
+}
+
+// chunks of kNodeChunk rules a node's list is cut into (a node without rules
+// still has one: its block stores the zero row)
+__global__ void k_profile_chunks(const int64_t* __restrict__ nt_off, int32_t N, int32_t* __restrict__ cnt) {
+  const int32_t n = blockIdx.x * blockDim.x + threadIdx.x;
+  if (n >= N) return;
+  const int64_t len = nt_off[n + 1] - nt_off[n];
+  cnt[n] = int32_t(len <= kNodeChunk ? 1 : (len + kNodeChunk - 1) / kNodeChunk);
+}
+
+// block (x, y): chunk x of the nodes' rule lists (chunk_off [N+1] = exclusive
+// scan of the chunk counts), bucket tile y.  A single-chunk node's cells go
+// straight to out, a heavy node's partial sums to part [chunk][B].
+__global__ __launch_bounds__(256) void k_profile_nodes(const int64_t* __restrict__ nt_off,
+                                                        const int32_t* __restrict__ nt_rule,
+                                                        const int64_t* __restrict__ chunk_off, int32_t N,
+                                                        const int32_t* __restrict__ rc, int32_t B,
+                                                        int64_t* __restrict__ out, int64_t* __restrict__ part) {
+  const int64_t ch = blockIdx.x;
+  if (ch >= chunk_off[N]) return;
+  // the node of chunk ch: the last n with chunk_off[n] <= ch
+  int32_t n0 = 0, n1 = N - 1;
+  while (n0 < n1) {
+    const int32_t mid = (n0 + n1 + 1) >> 1;
+    if (chunk_off[mid] <= ch) n0 = mid;
+    else n1 = mid - 1;
+  }
+  const int32_t n = n0;
+  const int64_t c0 = chunk_off[n], nch = chunk_off[n + 1] - c0;
+  const int64_t beg = nt_off[n] + (ch - c0) * kNodeChunk;
+  const int64_t lend = nt_off[n + 1], end = beg + kNodeChunk < lend ? beg + kNodeChunk : lend;
+  const TileLane t = tile_lane(B);
+  int64_t acc = 0;
+  if (t.active) {
+    // four independent (rule index, row) load pairs in flight per lane
+    const int64_t step = t.slots;
+    int64_t j = beg + t.slot;
+    for (; j + 3 * step < end; j += 4 * step) {
+      const int64_t r0 = nt_rule[j], r1 = nt_rule[j + step], r2 = nt_rule[j + 2 * step], r3 = nt_rule[j + 3 * step];
+      const int32_t x0 = rc[r0 * B + t.col], x1 = rc[r1 * B + t.col], x2 = rc[r2 * B + t.col],
+                    x3 = rc[r3 * B + t.col];
+      acc += int64_t(x0) + x1 + x2 + x3;
+    }
+    for (; j < end; j += step) acc += rc[int64_t(nt_rule[j]) * B + t.col];
+  }
+  const int64_t sum = tile_reduce(t, acc);
+  if (int32_t(threadIdx.x) < t.W && t.col < B) {
+    if (nch == 1) out[int64_t(n) * B + t.col] = sum;
+    else part[ch * B + t.col] = sum;
+  }
+}
+
+// the cells of nodes with more than one chunk: the sum of their partials
+__global__ __launch_bounds__(256) void k_profile_nodes_reduce(const int64_t* __restrict__ chunk_off, int32_t N,
+                                                               int32_t B, const int64_t* __restrict__ part,
+                                                               int64_t* __restrict__ out) {
+  const int64_t i = blockIdx.x * int64_t(blockDim.x) + threadIdx.x;
+  if (i >= int64_t(N) * B) return;
+  const int64_t n = i / B;
+  const int32_t col = int32_t(i - n * B);
+  const int64_t c0 = chunk_off[n], c1 = chunk_off[n + 1];
+  if (c1 - c0 <= 1) return;
+  int64_t sum = 0;
+  for (int64_t c = c0; c < c1; c++) sum += part[c * B + col];
+  out[i] = sum;
+}
+
+// ------------------------------------------------------------------ host --
+int profile_check_args(const char* what, const cg_ctx* c, const cg_specs* s, const cg_zone* z, int64_t width,
+                       int32_t n_buckets) {
+  if (!c || !s || !z) return cg_fail(CG_EINVAL, std::string(what) + ": null");
+  if (n_buckets < 1 || n_buckets > kMaxBuckets)
+    return cg_fail(CG_EINVAL, std::string(what) + ": n_buckets must be in [1, " + std::to_string(kMaxBuckets) + "]");
+  if (width < 1) return cg_fail(CG_EINVAL, std::string(what) + ": width must be at least 1 second");
+  if (width > CG_MAX_HORIZON / n_buckets)
+    return cg_fail(CG_ERANGE, std::string(what) + ": n_buckets * width exceeds CG_MAX_HORIZON (40 years)");
+  return CG_OK;
+}
+
+int ensure_events(cg_ctx* c) {
+  for (hipEvent_t& e : c->pfev)
+    if (!e) HIPCHK(hipEventCreateWithFlags(&e, hipEventDisableSystemFence));
+  return CG_OK;
+}
+
+// count chain + rule matrix + totals, enqueued on the ctx stream (the caller
+// drains it); c->mu held.  pfev[0..3] bracket the three kernels (pfev[3]:
+// the end of the totals, where a per-node call's join starts).
+int profile_rules_enqueue(cg_ctx* c, const cg_specs* s, const cg_zone* z, int64_t t0, int64_t w, int32_t B) {
+  c->pf_valid = false;
+  c->pf_has_nodes = false;
+  int rc;
+  bool empty = true;
+  if ((rc = sync_count_scan(c, s, z, t0, t0 + int64_t(B) * w, &empty))) return rc;
+  if ((rc = ensure_events(c))) return rc;
+  const int64_t R = int64_t(s->n);
+  if ((rc = c->pf_rules.ensure(size_t(std::max<int64_t>(R * B, 1)))) || (rc = c->pf_totals.ensure(size_t(B))))
+    return rc;
+  hipStream_t st = c->st;
+  HIPCHK(hipMemsetAsync(c->pf_totals.p, 0, size_t(B) * 8, st));
+  for (int i = 14; i < 19; i++) c->kt[i] = 0.f;
+  for (int i = 0; i < 4; i++) (void)hipEventRecord(c->pfev[i], st);
+  if (!empty) {
+    RunSet& rs = c->rs;
+    // a rule whose reference loop never ends: refuse before any cell is computed
+    HIPCHK(hipStreamSynchronize(st));
+    const unsigned long long stuck = static_cast<unsigned long long>(rs.res_host[1]);
+    if (stuck != ~0ULL) return cg_fail(CG_ERANGE, stuck_msg(stuck));
+    const size_t lds = plan_lds_bytes(rs.pa);
+    (void)hipEventRecord(c->pfev[0], st);
+    hipLaunchKernelGGL(k_profile_rules, dim3(gridn(R * B, 256, 4096)), dim3(256), lds, st, s->d, R, rs.pa,
+                       rs.run_anchor.p, rs.run_count.p, rs.run_dmask.p, w, B, c->pf_rules.p);
+    (void)hipEventRecord(c->pfev[1], st);
+    if (rs.has_walk())
+      hipLaunchKernelGGL(k_profile_walk, dim3(gridn(R, 256, 256 * 16)), dim3(256), lds, st, s->d, R, rs.pa,
+                         rs.run_anchor.p, rs.run_count.p, rs.run_dmask.p, w, B, c->pf_rules.p);
+    (void)hipEventRecord(c->pfev[2], st);
+    hipLaunchKernelGGL(k_profile_totals, dim3(gridn(R, kTotalChunk, 1 << 30), (B + 63) / 64), dim3(256), 0, st,
+                       c->pf_rules.p, R, B, reinterpret_cast<unsigned long long*>(c->pf_totals.p));
+    (void)hipEventRecord(c->pfev[3], st);
+    HIPCHK(hipGetLastError());
+  }
+  c->pf_R = R;
+  c->pf_B = B;
+  c->pf_N = 0;
+  return CG_OK;
+}
+
+void profile_rule_times(cg_ctx* c) {
+  for (int i = 0; i < 3; i++) (void)hipEventElapsedTime(&c->kt[14 + i], c->pfev[i], c->pfev[i + 1]);
+  // the count and scan behind it, when the chain recorded their events ([0], [1])
+  if (c->phase_timing >= 2 && c->pf_R > 0) {
+    (void)hipEventElapsedTime(&c->kt[0], c->ev[0], c->ev[1]);
+    (void)hipEventElapsedTime(&c->kt[1], c->ev[1], c->ev[2]);
+  }
+}
+
+int profile_no_result() { return cg_fail(CG_EINVAL, "no profile result (the last profile call failed, or none was made)"); }
+
+}  // namespace
+
+extern "C" {
+
+int cg_profile_device(cg_ctx* c, const cg_specs* s, const cg_zone* z, int64_t t0, int64_t width, int32_t n_buckets) {
+  if (int rc = profile_check_args("cg_profile_device", c, s, z, width, n_buckets)) return rc;
+  std::lock_guard<std::mutex> g(c->mu);
+  (void)hipGetLastError();  // clear a stale error so launch checks see only their own
+  int rc = profile_rules_enqueue(c, s, z, t0, width, n_buckets);
+  if (rc) return rc;
+  HIPCHK(hipStreamSynchronize(c->st));
+  profile_rule_times(c);
+  c->pf_valid = true;
+  return CG_OK;
+}
+
+int cg_profile_per_node_device(cg_ctx* c, const cg_specs* s, const cg_zone* z, int64_t t0, int64_t width,
+                               int32_t n_buckets, const cg_rules* rules, int mode) {
+  if (int rc = profile_check_args("cg_profile_per_node_device", c, s, z, width, n_buckets)) return rc;
+  if (!rules) return cg_fail(CG_EINVAL, "cg_profile_per_node_device: null");
+  if (mode < 0 || mode > 2) return cg_fail(CG_EINVAL, "bad exclude mode");
+  const RulesStore& in = rules->st;
+  if (int64_t(s->n) != in.n_rules) return cg_fail(CG_EINVAL, "specs count != rules n_rules");
+  std::lock_guard<std::mutex> g(c->mu);
+  (void)hipGetLastError();
+  const int32_t B = n_buckets, N = in.n_nodes;
+  int rc = profile_rules_enqueue(c, s, z, t0, width, B);
+  if (rc) return rc;
+  hipStream_t st = c->st;
+  // the rule->node join and its transpose: the per-node path's cache, keyed
+  // by (rule set, exclude mode); rebuilt here on a miss (the cached segment
+  // bounds go with the old transpose), its keys set once the stream drained
+  const bool cached = in.serial != 0 && in.serial == c->pn_cache_serial && mode == c->pn_cache_mode;
+  int64_t nnz = c->pn_nnz;
+  if (!cached) {
+    c->pn_cache_serial = 0;
+    c->pn_K = 0;
+    if ((rc = rule_nodes_locked(c, in, mode, &nnz)) || (rc = transpose_locked(c, nnz, N))) return rc;
+  }
+  (void)hipEventRecord(c->pfev[4], st);
+  const int64_t chunks_max = int64_t(N) + nnz / kNodeChunk + 1;  // >= the chunk total
+  if ((rc = c->pf_nodes.ensure(size_t(std::max<int64_t>(int64_t(N) * B, 1)))) ||
+      (rc = c->pf_part.ensure(size_t(chunks_max * B))) || (rc = c->pf_chunk_cnt.ensure(size_t(std::max(N, 1)))) ||
+      (rc = c->pf_chunk_off.ensure(size_t(N) + 1)) ||
+      (rc = c->scan_tmp.ensure(std::max(c->scan_tmp.cap, scan_temp_bytes(std::max(N, 1))))))
+    return rc;
+  if (N > 0) {
+    hipLaunchKernelGGL(k_profile_chunks, dim3(gridn(N, 256, 1 << 30)), dim3(256), 0, st, c->nt_off.p, N,
+                       c->pf_chunk_cnt.p);
+    launch_scan(c->pf_chunk_cnt.p, c->pf_chunk_off.p, N, c->scan_tmp.p, st);
+    hipLaunchKernelGGL(k_profile_nodes, dim3(unsigned(chunks_max), (B + 63) / 64), dim3(256), 0, st, c->nt_off.p,
+                       c->nt_rule.p, c->pf_chunk_off.p, N, c->pf_rules.p, B, c->pf_nodes.p, c->pf_part.p);
+    hipLaunchKernelGGL(k_profile_nodes_reduce, dim3(gridn(int64_t(N) * B, 256, 1 << 30)), dim3(256), 0, st,
+                       c->pf_chunk_off.p, N, B, c->pf_part.p, c->pf_nodes.p);
+  }
+  (void)hipEventRecord(c->pfev[5], st);
+  HIPCHK(hipGetLastError());
+  HIPCHK(hipStreamSynchronize(st));
+  if (!cached) {
+    c->pn_nnz = nnz;
+    c->pn_cache_serial = in.serial;
+    c->pn_cache_mode = mode;
+  }
+  profile_rule_times(c);
+  if (!cached) (void)hipEventElapsedTime(&c->kt[17], c->pfev[3], c->pfev[4]);  // 0: the cached join was reused
+  (void)hipEventElapsedTime(&c->kt[18], c->pfev[4], c->pfev[5]);
+  c->pf_N = N;
+  c->pf_has_nodes = true;
+  c->pf_valid = true;
+  return CG_OK;
+}
+
+int cg_profile_result_device(cg_ctx* c, const int32_t** d_rule_counts, const int64_t** d_bucket_totals,
+                             const int64_t** d_node_counts, int64_t* n_rules, int32_t* n_nodes, int32_t* n_buckets) {
+  if (!c) return cg_fail(CG_EINVAL, "cg_profile_result_device: null");
+  std::lock_guard<std::mutex> g(c->mu);
+  if (!c->pf_valid) return profile_no_result();
+  if (d_rule_counts) *d_rule_counts = c->pf_rules.p;
+  if (d_bucket_totals) *d_bucket_totals = c->pf_totals.p;
+  if (d_node_counts) *d_node_counts = c->pf_has_nodes ? c->pf_nodes.p : nullptr;
+  if (n_rules) *n_rules = c->pf_R;
+  if (n_nodes) *n_nodes = c->pf_has_nodes ? c->pf_N : 0;
+  if (n_buckets) *n_buckets = c->pf_B;
+  return CG_OK;
+}
+
+int cg_profile_copy_rules(cg_ctx* c, int64_t first_rule, int64_t count, int32_t* out) {
+  if (!c || (count > 0 && !out)) return cg_fail(CG_EINVAL, "cg_profile_copy_rules: null");
+  std::lock_guard<std::mutex> g(c->mu);
+  if (!c->pf_valid) return profile_no_result();
+  if (first_rule < 0 || count < 0 || first_rule + count > c->pf_R)
+    return cg_fail(CG_EINVAL, "rule range outside the last profile");
+  (void)hipGetLastError();
+  HIPCHK(hipSetDevice(c->device));
+  if (count)
+    HIPCHK(hipMemcpy(out, c->pf_rules.p + first_rule * c->pf_B, size_t(count) * c->pf_B * 4, hipMemcpyDeviceToHost));
+  return CG_OK;
+}
+
+int cg_profile_copy_totals(cg_ctx* c, int64_t* out) {
+  if (!c || !out) return cg_fail(CG_EINVAL, "cg_profile_copy_totals: null");
+  std::lock_guard<std::mutex> g(c->mu);
+  if (!c->pf_valid) return profile_no_result();
+  (void)hipGetLastError();
+  HIPCHK(hipSetDevice(c->device));
+  HIPCHK(hipMemcpy(out, c->pf_totals.p, size_t(c->pf_B) * 8, hipMemcpyDeviceToHost));
+  return CG_OK;
+}
+
+int cg_profile_copy_nodes(cg_ctx* c, int32_t first_node, int32_t count, int64_t* out) {
+  if (!c || (count > 0 && !out)) return cg_fail(CG_EINVAL, "cg_profile_copy_nodes: null");
+  std::lock_guard<std::mutex> g(c->mu);
+  if (!c->pf_valid) return profile_no_result();
+  if (!c->pf_has_nodes) return cg_fail(CG_EINVAL, "the last profile has no node matrix (cg_profile_device)");
+  if (first_node < 0 || count < 0 || int64_t(first_node) + count > c->pf_N)
+    return cg_fail(CG_EINVAL, "node range outside the last profile");
+  (void)hipGetLastError();
+  HIPCHK(hipSetDevice(c->device));
+  if (count)
+    HIPCHK(hipMemcpy(out, c->pf_nodes.p + int64_t(first_node) * c->pf_B, size_t(count) * c->pf_B * 8,
+                     hipMemcpyDeviceToHost));
+  return CG_OK;
+}
+
+}  // extern "C"

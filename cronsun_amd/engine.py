@@ -10,6 +10,10 @@ seen from Python.  Wraps a cg_ctx (one HIP device + stream + HBM buffers).
   Engine.expand_device(specs, loc, t0, t1)  same, left in HBM (bench)
   Engine.expand_per_node(specs, loc, t0, t1, rules, mode)
                                             per-node (time, rule) CSR
+  Engine.profile(specs, loc, t0, width, n_buckets)
+                                            fires per (rule, bucket), no lists
+  Engine.profile_per_node(specs, loc, t0, width, n_buckets, drules, mode)
+                                            fires per (node, bucket)
 """
 import ctypes as C
 import threading
@@ -671,6 +675,106 @@ class Engine:
 
     def node_counts_to_device(self, d_ptr):
         check(lib().cg_node_counts_to_device(self._h, C.c_void_p(d_ptr)))
+
+    # ----------------------------------------------------- fire profile
+    def profile(self, specs, loc, t0, width, n_buckets):
+        """Fires per rule and bucket over n_buckets buckets of `width` seconds
+        from t0 (cg_profile_device; bucket b is (t0 + b*width, t0 +
+        (b+1)*width]): (rule_counts int32 [R, B], bucket_totals int64 [B]).
+        No fire list is written; a row sums to count()'s count."""
+        sp = self._specs(specs)
+        B = int(n_buckets)
+        check(lib().cg_profile_device(self._h, sp._h, self._loc(loc).handle, int(t0), int(width), B))
+        rules = np.empty((max(sp.n, 1), B), dtype=np.int32)
+        check(lib().cg_profile_copy_rules(self._h, 0, sp.n, rules.ctypes.data))
+        totals = np.empty(B, dtype=np.int64)
+        check(lib().cg_profile_copy_totals(self._h, totals.ctypes.data))
+        return rules[:sp.n], totals
+
+    def profile_per_node(self, specs, loc, t0, width, n_buckets, drules, mode=_lib.EXCLUDE_NONE):
+        """Fires per node and bucket (cg_profile_per_node_device): int64
+        [N, B], the sum of the rule counts over the rules each node runs under
+        the exclude mode -- what binning expand_per_node's lists would give.
+        `drules` is an uploaded rule set (upload_rules).  The rule matrix and
+        totals of the same call: profile_rules() / profile_totals()."""
+        B = int(n_buckets)
+        check(lib().cg_profile_per_node_device(self._h, specs._h, self._loc(loc).handle, int(t0), int(width), B,
+                                               drules._h, int(mode)))
+        return self.profile_nodes()
+
+    def profile_result_device(self):
+        """Device pointers and shape of the last profile: (rule_counts,
+        bucket_totals, node_counts or None, n_rules, n_nodes, n_buckets)."""
+        r, t, n = C.c_void_p(), C.c_void_p(), C.c_void_p()
+        R, N, B = C.c_int64(), C.c_int32(), C.c_int32()
+        check(lib().cg_profile_result_device(self._h, C.byref(r), C.byref(t), C.byref(n), C.byref(R), C.byref(N),
+                                             C.byref(B)))
+        return r.value, t.value, n.value, R.value, N.value, B.value
+
+    def profile_rules(self, first=0, count=None):
+        """Rows [first, first+count) of the last profile's rule matrix (host int32 [count, B])."""
+        _, _, _, R, _, B = self.profile_result_device()
+        count = R - first if count is None else int(count)
+        out = np.empty((max(count, 1), B), dtype=np.int32)
+        check(lib().cg_profile_copy_rules(self._h, int(first), count, out.ctypes.data))
+        return out[:count]
+
+    def profile_totals(self):
+        """The last profile's bucket totals (host int64 [B])."""
+        B = self.profile_result_device()[5]
+        out = np.empty(B, dtype=np.int64)
+        check(lib().cg_profile_copy_totals(self._h, out.ctypes.data))
+        return out
+
+    def profile_nodes(self, first=0, count=None):
+        """Rows [first, first+count) of the last profile's node matrix (host int64 [count, B])."""
+        _, _, _, _, N, B = self.profile_result_device()
+        count = N - first if count is None else int(count)
+        out = np.empty((max(count, 1), B), dtype=np.int64)
+        check(lib().cg_profile_copy_nodes(self._h, int(first), count, out.ctypes.data))
+        return out[:count]
+
+    def _profile_tensors(self):
+        import torch
+        r, t, n, R, N, B = self.profile_result_device()
+
+        class _View:
+            def __init__(self, ptr, shape, typestr):
+                self.__cuda_array_interface__ = {"shape": shape, "typestr": typestr,
+                                                 "data": (ptr, False), "version": 3}
+        dev = torch.device("cuda", self.device)
+
+        def view(ptr, rows, typestr, dtype):
+            if rows == 0:
+                return torch.zeros((0, B), dtype=dtype, device=dev)
+            return torch.as_tensor(_View(ptr, (rows, B), typestr), device=dev)
+        rules = view(r, R, "<i4", torch.int32)
+        totals = torch.as_tensor(_View(t, (B,), "<i8"), device=dev)
+        nodes = None if n is None else view(n, N, "<i8", torch.int64)
+        return rules, totals, nodes
+
+    def profile_device(self, specs, loc, t0, width, n_buckets):
+        """profile() left in HBM: zero-copy torch views (rule_counts int32
+        [R, B], bucket_totals int64 [B]) of the engine's profile buffers,
+        valid until the next profile call (__cuda_array_interface__)."""
+        check(lib().cg_profile_device(self._h, specs._h, self._loc(loc).handle, int(t0), int(width),
+                                      int(n_buckets)))
+        return self._profile_tensors()[:2]
+
+    def profile_per_node_device(self, specs, loc, t0, width, n_buckets, drules, mode=_lib.EXCLUDE_NONE):
+        """profile_per_node() left in HBM: torch views (rule_counts int32
+        [R, B], bucket_totals int64 [B], node_counts int64 [N, B])."""
+        check(lib().cg_profile_per_node_device(self._h, specs._h, self._loc(loc).handle, int(t0), int(width),
+                                               int(n_buckets), drules._h, int(mode)))
+        return self._profile_tensors()
+
+    def profile_kernel_times(self):
+        """ms of the last profile call (cg_last_kernel_times [14..18]):
+        k_profile_rules, k_profile_walk, k_profile_totals, join + transpose
+        (0 when the cached join was reused), node matrix."""
+        buf = (C.c_float * 19)()
+        check(lib().cg_last_kernel_times(self._h, buf, 19))
+        return list(buf)[14:19]
 
     def fill(self, d_ptr, nbytes, byte_value=0xFF):
         """Fill a device buffer with one byte value (cg_fill_device)."""

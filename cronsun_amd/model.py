@@ -7,6 +7,8 @@ libcronsun_gpu.so (cg_jobset_*).
   Job.IsRunOn(nid, groups)         job.go:616-630
   Job.GetJobNodes(groups)          web/job.go:222-257 (cumulative excludes)
   JobSet.lock_ttls(now, loc)       Cmd.lockTtl (job.go:194-233) for every rule
+  JobSet.node_profile(t0, width, n_buckets)
+                                   fires per node and bucket ahead of time
   JobSet(jobs, groups)             all jobs interned at once -> RulesIn for the
                                    GPU per-node expansion (node/node.go:121-158
                                    for every node at once)
@@ -177,6 +179,24 @@ class JobSet(_Interned):
         kind = np.array([self.jobs[j].Kind for j in self.rule_job], dtype=np.int32)
         avg = np.array([self.jobs[j].AvgTime for j in self.rule_job], dtype=np.int64)
         return eng.lock_ttl_batch(self.schedules(), loc, now, kind, avg, lock_ttl)
+
+    def node_profile(self, t0, width, n_buckets, loc=None, mode=_lib.EXCLUDE_NONE, engine=None):
+        """Commands started per node and bucket over n_buckets buckets of
+        `width` seconds from t0 (Engine.profile_per_node): {node ID: int64
+        [n_buckets]} -- the load each cronnode's own Cron (node/node.go:121-158,
+        node/cron/cron.go:210-275) is about to take, before anything has run
+        (the reference only has the executed-jobs statistics, web/info.go:14-22)."""
+        from .engine import default_engine
+        eng = engine or default_engine()
+        rin = self.rules_in()
+        specs = eng.upload(self.schedules())
+        drules = eng.upload_rules(rin)
+        try:
+            counts = eng.profile_per_node(specs, loc, t0, width, n_buckets, drules, mode)
+        finally:
+            drules.free()
+            specs.free()
+        return {self.node_id(n): counts[n] for n in range(rin.n_nodes)}
 
     def schedules(self):
         """Parsed schedules in rule order (JobRule.Valid on each)."""

@@ -330,7 +330,9 @@ int cg_result_copy_offsets(cg_ctx* ctx, int64_t* host_offsets /* [R+1] */);
  * join, [7] transpose (when the join is rebuilt) + segment records + per-node
  * offsets, [8] per-node write; [12] the last time-order pass; of the last
  * dispatcher wake: [9] scan, [10] due compaction, [11] advance; [13] the last
- * cg_dispatcher_fanout.  n = entries written. */
+ * cg_dispatcher_fanout; of the last profile call: [14] rule matrix, [15]
+ * walked runs, [16] totals, [17] join + transpose (when rebuilt), [18] node
+ * matrix.  n = entries written. */
 int cg_last_kernel_times(cg_ctx* ctx, float* ms, int n);
 /* Expansion phase timing: 2 (default) = a HIP event between every phase;
  * 1 = events around k_write_cf only ([3]; [0..2], [4], [5] read -1).  Events
@@ -531,6 +533,52 @@ int cg_expand_per_node_rules_device_async(cg_ctx* ctx, const cg_specs* specs, co
 /* *n_events: the last window's node events (its result is then readable);
  * *n_events_all (may be NULL): the node events of every window waited for. */
 int cg_expand_per_node_wait(cg_ctx* ctx, int64_t* n_events, int64_t* n_events_all);
+
+/* ---------------------------------------------------------- fire profile --- */
+/* How many commands start per bucket of time, per rule, cluster-wide and on
+ * each node, over the coming day or week: the forward-looking counterpart of
+ * the reference's only load view, the executed-jobs statistics kept after the
+ * fact (web/info.go:14-22, job_log.go:135-150).  No fire list is written.
+ *
+ * Buckets are fixed-width in unix seconds: with t1 = t0 + n_buckets * width,
+ * bucket b is (t0 + b*width, t0 + (b+1)*width].
+ *   rule_counts[r][b]  int32, row-major [R][B]: the fires of rule r's
+ *       expansion over the whole of (t0, t1] (exactly cg_expand's: @every is
+ *       anchored at t0, a rule that stops stops) that fall in bucket b; a row
+ *       sums to cg_count's count
+ *   bucket_totals[b]   int64 [B]: the column sums
+ *   node_counts[n][b]  int64, row-major [N][B]: the sum of rule_counts[r][b]
+ *       over the rules node n runs under the exclude mode -- the join of
+ *       cg_expand_per_node_rules_device (job.go:591-630 / web/job.go:222-257:
+ *       pause, the last-rule-wins Cmd keys, all three modes), i.e. what
+ *       binning the per-node lists would give
+ * width < 1 or n_buckets outside [1, 4096]: CG_EINVAL; n_buckets * width >
+ * CG_MAX_HORIZON: CG_ERANGE; a specs count other than the rule set's n_rules:
+ * CG_EINVAL (all before any device work).  A rule whose reference loop never
+ * ends inside the horizon: CG_ERANGE naming the rule, as cg_expand.  No rule:
+ * valid, zero totals.
+ * Synchronous, on the ctx's stream.  Like cg_count the calls drain pending
+ * pipelined calls (cg_expand_device_async, the per-node windows), discard
+ * their results and errors, and leave no expansion result behind.  The
+ * per-node call reuses the rule->node join a per-node expansion on the same
+ * rule set and mode left (and leaves its own for the next).  The profile
+ * stays readable until the next profile call or cg_destroy: expansion calls
+ * do not touch it.  cg_last_kernel_times [14..18]: rule matrix, walked runs,
+ * totals, join + transpose (when rebuilt), node matrix. */
+int cg_profile_device(cg_ctx* ctx, const cg_specs* specs, const cg_zone* z, int64_t t0,
+                      int64_t width, int32_t n_buckets);
+int cg_profile_per_node_device(cg_ctx* ctx, const cg_specs* specs, const cg_zone* z, int64_t t0,
+                               int64_t width, int32_t n_buckets, const cg_rules* rules, int mode);
+/* Device pointers and shape of the last profile (any out pointer may be NULL).
+ * After cg_profile_device there is no node matrix: *d_node_counts = NULL,
+ * *n_nodes = 0.  CG_EINVAL when no profile is readable. */
+int cg_profile_result_device(cg_ctx* ctx, const int32_t** d_rule_counts,
+                             const int64_t** d_bucket_totals, const int64_t** d_node_counts,
+                             int64_t* n_rules, int32_t* n_nodes, int32_t* n_buckets);
+/* copy rows [first, first+count) of the rule / node matrix, or the totals, to host */
+int cg_profile_copy_rules(cg_ctx* ctx, int64_t first_rule, int64_t count, int32_t* out /* [count*B] */);
+int cg_profile_copy_totals(cg_ctx* ctx, int64_t* out /* [B] */);
+int cg_profile_copy_nodes(cg_ctx* ctx, int32_t first_node, int32_t count, int64_t* out /* [count*B] */);
 
 /* ------------------------------------------- dispatcher node fan-out ---- */
 /* One dispatcher table for a whole cluster: after a wake, which node runs

@@ -411,6 +411,78 @@ func (e *Engine) ExpandPerNode(sp *Specs, z *Zone, t0, t1 time.Time, j *Jobset, 
 	return res, nil
 }
 
+// Profile counts, without writing any fire list, the fires of every rule in
+// each of nBuckets buckets of `width` from t0 (bucket b is (t0 + b*width,
+// t0 + (b+1)*width]): ruleCounts[r*nBuckets+b] and the column sums totals[b].
+// It is the forward-looking counterpart of the executed-jobs statistics the
+// reference keeps after the fact (web/info.go:14-22, job_log.go:135-150).
+func (e *Engine) Profile(sp *Specs, z *Zone, t0 time.Time, width time.Duration, nBuckets int) (ruleCounts []int32, totals []int64, err error) {
+	defer runtime.KeepAlive(e)
+	defer runtime.KeepAlive(sp)
+	defer runtime.KeepAlive(z)
+	if rc := C.cg_profile_device(e.ctx, sp.s, z.z, C.int64_t(t0.Unix()), C.int64_t(width/time.Second),
+		C.int32_t(nBuckets)); rc != 0 {
+		return nil, nil, lastErr(rc)
+	}
+	return e.profileRules(sp.n, nBuckets)
+}
+
+// profileRules copies the rule matrix and totals of the last profile call.
+func (e *Engine) profileRules(nRules, nBuckets int) ([]int32, []int64, error) {
+	ruleCounts := make([]int32, nRules*nBuckets)
+	if len(ruleCounts) > 0 {
+		if rc := C.cg_profile_copy_rules(e.ctx, 0, C.int64_t(nRules), (*C.int32_t)(unsafe.Pointer(&ruleCounts[0]))); rc != 0 {
+			return nil, nil, lastErr(rc)
+		}
+	}
+	totals := make([]int64, nBuckets)
+	if rc := C.cg_profile_copy_totals(e.ctx, (*C.int64_t)(unsafe.Pointer(&totals[0]))); rc != 0 {
+		return nil, nil, lastErr(rc)
+	}
+	return ruleCounts, totals, nil
+}
+
+// ProfilePerNode is Profile summed per node: node ID -> fires per bucket of
+// the rules that node runs (every node's loadJobs -> Job.Cmds filter,
+// node/node.go:121-158, job.go:591-614, under the exclude mode), i.e. what
+// binning ExpandPerNode's lists would give; totals are Profile's (a rule's
+// fire counts once, on however many nodes it runs).
+func (e *Engine) ProfilePerNode(sp *Specs, z *Zone, t0 time.Time, width time.Duration, nBuckets int, j *Jobset, mode int) (nodes map[string][]int64, totals []int64, err error) {
+	defer runtime.KeepAlive(e)
+	defer runtime.KeepAlive(sp)
+	defer runtime.KeepAlive(z)
+	defer runtime.KeepAlive(j)
+	var rin C.cg_rules_in
+	if rc := C.cg_jobset_rules(j.js, &rin); rc != 0 {
+		return nil, nil, lastErr(rc)
+	}
+	var r *C.cg_rules
+	if rc := C.cg_rules_upload(e.ctx, &rin, &r); rc != 0 {
+		return nil, nil, lastErr(rc)
+	}
+	defer C.cg_rules_free(r) // the node matrix stays in the engine's own buffers
+	if rc := C.cg_profile_per_node_device(e.ctx, sp.s, z.z, C.int64_t(t0.Unix()), C.int64_t(width/time.Second),
+		C.int32_t(nBuckets), r, C.int(mode)); rc != 0 {
+		return nil, nil, lastErr(rc)
+	}
+	nn := int(rin.n_nodes)
+	counts := make([]int64, nn*nBuckets)
+	if len(counts) > 0 {
+		if rc := C.cg_profile_copy_nodes(e.ctx, 0, C.int32_t(nn), (*C.int64_t)(unsafe.Pointer(&counts[0]))); rc != 0 {
+			return nil, nil, lastErr(rc)
+		}
+	}
+	totals = make([]int64, nBuckets)
+	if rc := C.cg_profile_copy_totals(e.ctx, (*C.int64_t)(unsafe.Pointer(&totals[0]))); rc != 0 {
+		return nil, nil, lastErr(rc)
+	}
+	nodes = make(map[string][]int64, nn)
+	for n := 0; n < nn; n++ {
+		nodes[C.GoString(C.cg_jobset_node_id(j.js, C.int32_t(n)))] = counts[n*nBuckets : (n+1)*nBuckets]
+	}
+	return nodes, totals, nil
+}
+
 // Dispatcher is Cron.run's entry table in HBM: slot = index into the caller's
 // Entry slice (c.indexes).  The run loop keeps its shape:
 //
