@@ -103,15 +103,16 @@ inline int64_t slice_map_words(int64_t cap) { return u_map_base(cap) + 2 * (kUSl
 size_t plan_lds_bytes(const PlanArgs& p);
 
 // *out += order-sensitive checksum of n elements (int64 or int32) of v,
-// positions first.., values + add (cg_checksum_device)
+// positions first.., values + add, both mod 2^64 (cg_checksum_device)
 void launch_checksum(const void* v, int64_t n, int elem_bytes, int64_t first, int64_t add,
                      unsigned long long* out, hipStream_t st);
 
-// *out += count of elements (int64 or int32) of v equal to x (cg_count_value_device)
 // streaming fill of n16 16-B words (store-ceiling probe of cg_fill_rate_device):
 // nt = 1 nontemporal stores, 0 plain
 void launch_fill_stream(void* p, int64_t n16, int nt, hipStream_t st);
 
+// *out += count of elements (int64 or int32) of v equal to x; an x outside the
+// int32 range equals no int32 element (cg_count_value_device)
 void launch_count_eq(const void* v, int64_t n, int elem_bytes, int64_t x, unsigned long long* out,
                      hipStream_t st);
 

@@ -816,10 +816,13 @@ template <class T>
 __global__ __launch_bounds__(256) void k_checksum(const T* __restrict__ v, int64_t n, int64_t first,
                                                    int64_t add, unsigned long long* __restrict__ out) {
   uint64_t acc = 0;
+  // both sums wrap mod 2^64 (unsigned: no signed overflow at the extremes);
+  // an int32 element is sign-extended first
+  const uint64_t ufirst = uint64_t(first), uadd = uint64_t(add);
   for (int64_t i = blockIdx.x * int64_t(blockDim.x) + threadIdx.x; i < n;
        i += int64_t(gridDim.x) * blockDim.x) {
-    const uint64_t x = uint64_t(int64_t(v[i]) + add);
-    acc += mix64(x ^ mix64(uint64_t(first + i) * 0x9E3779B97F4A7C15ull));
+    const uint64_t x = uint64_t(int64_t(v[i])) + uadd;
+    acc += mix64(x ^ mix64((ufirst + uint64_t(i)) * 0x9E3779B97F4A7C15ull));
   }
   for (int o = 32; o > 0; o >>= 1) acc += __shfl_xor(acc, o, 64);
   __shared__ uint64_t s[4];
@@ -894,6 +897,9 @@ void launch_checksum(const void* v, int64_t n, int elem_bytes, int64_t first, in
 void launch_count_eq(const void* v, int64_t n, int elem_bytes, int64_t x, unsigned long long* out,
                      hipStream_t st) {
   if (n <= 0) return;
+  // no int32 element equals a value outside the int32 range: the count stays 0
+  // (never the count of the value's low 32 bits)
+  if (elem_bytes == 4 && (x < INT32_MIN || x > INT32_MAX)) return;
   const int grid = grid_for(n, 256 * 8, 256 * 32);
   if (elem_bytes == 8)
     hipLaunchKernelGGL(k_count_eq<int64_t>, dim3(grid), dim3(256), 0, st, static_cast<const int64_t*>(v), n, x,

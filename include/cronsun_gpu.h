@@ -343,15 +343,23 @@ int cg_set_phase_timing(cg_ctx* ctx, int level);
 /* Order-sensitive checksum of a device array on the ctx's device
  * (instrumentation for integrity and parity checks; no reference
  * counterpart): sum over i < n of mix(first_index + i, v[i] + add) mod 2^64,
- * v = int64 (elem_bytes 8) or int32 (elem_bytes 4), mix = a 64-bit finaliser.
- * Checksums of consecutive ranges add up, so a shard's output (first_index =
- * its global base) can be compared with its range of another result. */
+ * v = int64 (elem_bytes 8) or int32 (elem_bytes 4, sign-extended to 64 bits).
+ * Both sums are taken mod 2^64 -- first_index + i and v[i] + add wrap like
+ * unsigned 64-bit integers, for any int64 first_index and add -- and
+ *   mix(p, x) = fin(x XOR fin(p * 0x9E3779B97F4A7C15 mod 2^64)),
+ * fin = the splitmix64 finaliser (shifts 30, 27, 31; multipliers
+ * 0xBF58476D1CE4E5B9, 0x94D049BB133111EB).
+ * Checksums of consecutive ranges add up (mod 2^64), so a shard's output
+ * (first_index = its global base) can be compared with its range of another
+ * result. */
 int cg_checksum_device(cg_ctx* ctx, const void* d_ptr, int64_t n, int elem_bytes,
                        int64_t first_index, int64_t add, uint64_t* out);
 /* Integrity helpers for benchmarks and tests (no reference counterpart):
  * fill `bytes` of a device buffer with one byte value (e.g. poison an output
  * before timed runs), and count the int64/int32 elements equal to `value`
- * (e.g. poison a later run left unwritten). */
+ * (e.g. poison a later run left unwritten).  `value` is compared as an int64:
+ * with elem_bytes 4 a value outside the int32 range equals no element, the
+ * count is 0 (it is never truncated to its low 32 bits). */
 int cg_fill_device(cg_ctx* ctx, void* d_ptr, int64_t bytes, int byte_value);
 int cg_count_value_device(cg_ctx* ctx, const void* d_ptr, int64_t n, int elem_bytes, int64_t value,
                           int64_t* count);
