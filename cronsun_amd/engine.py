@@ -260,7 +260,9 @@ class Dispatcher:
 
 
 def _as_c_schedules(schedules):
-    arr = (_lib.cg_schedule * max(len(schedules), 1))()
+    if isinstance(schedules, C.Array) and schedules._type_ is _lib.cg_schedule:
+        return schedules  # already a cg_schedule array (cron.parse_batch, a numpy view)
+    arr =(_lib.cg_schedule * max(len(schedules), 1))()
     for i, s in enumerate(schedules):
         arr[i] = s.to_c() if hasattr(s, "to_c") else s
     return arr
@@ -364,9 +366,15 @@ class Engine:
         return Specs(self, h, n)
 
     def upload_soa(self, second, minute, hour, dom, month, dow, delay_ns):
-        cols = [np.ascontiguousarray(x, dtype=np.uint64) for x in (second, minute, hour, dom, month, dow)]
+        """SoA upload (cg_specs_upload): delay_ns[i] > 0 makes rule i an @every
+        of that delay, else its six masks are read.  A mask column may be None
+        (NULL: reads as zero)."""
         d = np.ascontiguousarray(delay_ns, dtype=np.int64)
-        soa = _lib.cg_spec_soa(*[c.ctypes.data for c in cols], d.ctypes.data)
+        cols = [None if x is None else np.ascontiguousarray(x, dtype=np.uint64)
+                for x in (second, minute, hour, dom, month, dow)]
+        if any(c is not None and c.shape != d.shape for c in cols):
+            raise ValueError("upload_soa: one mask per rule in every column")
+        soa = _lib.cg_spec_soa(*[None if c is None else c.ctypes.data for c in cols], d.ctypes.data)
         h = C.c_void_p()
         check(lib().cg_specs_upload(self._h, C.byref(soa), len(d), C.byref(h)))
         return Specs(self, h, len(d))
@@ -411,7 +419,14 @@ class Engine:
         """Cron.run start (cron.go:212-215) over `specs` at `now`."""
         sp = self._specs(specs)
         h = C.c_void_p()
-        check(lib().cg_dispatcher_new(self._h, sp._h, self._loc(loc).handle, int(now), C.byref(h)))
+        rc = lib().cg_dispatcher_new(self._h, sp._h, self._loc(loc).handle, int(now), C.byref(h))
+        if rc < 0 and h:
+            # a stuck entry (CG_ERANGE): the dispatcher was built and handed
+            # back with the error; keep the message, free the table
+            err = CgError(rc, _lib.last_error())
+            lib().cg_dispatcher_free(h)
+            raise err
+        check(rc)
         return Dispatcher(self, h)
 
     # -------------------------------------------------------- expansion

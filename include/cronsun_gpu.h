@@ -216,7 +216,19 @@ int cg_lock_ttl_batch(cg_ctx* ctx, const cg_specs* specs, const cg_zone* z, cons
  *   cg_dispatcher_snapshot   Entries() (cron.go:166-174, 296-308): Next, Prev
  *                            and liveness per slot (any pointer may be NULL).
  * A schedule whose Next never returns (the reference loop then blocks
- * forever) makes the call fail with CG_ERANGE naming the slot. */
+ * forever) makes the call fail with CG_ERANGE naming the lowest such slot.
+ * Such a failed new / fire / set has otherwise taken effect: every other
+ * entry of the call is placed or advanced exactly, the due list of a failed
+ * fire is readable with cg_dispatcher_due, and the effective time is the
+ * minimum over the other entries.  The stuck slot stays live with Next =
+ * CG_NO_PROGRESS_TIME (a failed fire has set its Prev), never fires and never
+ * holds the effective time until it is replaced or removed.
+ * cg_dispatcher_new writes *out once the table is built: a failure before
+ * that (bad arguments, no memory, `now` out of range) leaves *out as the
+ * caller set it, and on this CG_ERANGE *out holds the dispatcher just
+ * described.  Set *out to NULL before the call; when it is not NULL after a
+ * failed one, the caller must free it with cg_dispatcher_free (or, after this
+ * CG_ERANGE, may go on with it). */
 typedef struct cg_dispatcher cg_dispatcher;
 int cg_dispatcher_new(cg_ctx* ctx, const cg_specs* specs, const cg_zone* z, int64_t now,
                       cg_dispatcher** out);
