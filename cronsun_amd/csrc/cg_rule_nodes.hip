@@ -281,7 +281,7 @@ int validate_rules(const cg_rules_in* in) {
       seen[j] = 1;
     }
   }
-  auto check_list = [&](const int64_t* off, const int32_t* v, int64_t cnt, int32_t lim,
+  auto check_list = [&](const int64_t* off, const int32_t* v, int64_t cnt, int64_t lim,
                         const char* what) -> int {
     if (off[0] != 0) return cg_fail(CG_EINVAL, std::string(what) + ": offsets must start at 0");
     for (int64_t i = 0; i < cnt; i++)
@@ -294,7 +294,8 @@ int validate_rules(const cg_rules_in* in) {
   if (in->n_rules) {
     if ((rc = check_list(in->nid_off, in->nids, in->n_rules, in->n_nodes, "nids"))) return rc;
     if ((rc = check_list(in->gid_off, in->gids, in->n_rules, in->n_groups, "gids"))) return rc;
-    if ((rc = check_list(in->ex_off, in->ex, in->n_rules, INT32_MAX, "exclude_nids"))) return rc;
+    // an ExcludeNodeID may name a node the cluster no longer has: any id >= 0
+    if ((rc = check_list(in->ex_off, in->ex, in->n_rules, int64_t(INT32_MAX) + 1, "exclude_nids"))) return rc;
   }
   if (in->n_groups && (rc = check_list(in->group_off, in->group_nodes, in->n_groups, in->n_nodes, "groups")))
     return rc;

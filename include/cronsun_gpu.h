@@ -428,6 +428,23 @@ typedef struct {
    * cg_jobset_rules fills it from the Rule.IDs. */
   const int32_t* rule_key;
 } cg_rules_in;
+/* Limits of a rule set.  nids, gids and group_nodes must be in range
+ * (CG_EINVAL otherwise); an ExcludeNodeID may be any id in [0, 2^31 - 1] --
+ * one at or past n_nodes excludes nothing.  The join keeps a rule's node set
+ * as a bitmap in the 64 KiB of LDS one wave may ask for, so a rule set has at
+ * most 524288 nodes, and at most 262144 when some job repeats a Cmd key
+ * (rule_key given and equal for two rules of one job: the later rules' sets
+ * take a second bitmap).  rule_key that repeats no key inside a job counts as
+ * NULL.  One node more and every call that builds the join -- cg_rule_nodes,
+ * cg_expand_per_node*, cg_profile_per_node_device, cg_dispatcher_bind_rules,
+ * cg_dispatcher_patch_rules for its patch -- fails with CG_ERANGE before any
+ * kernel runs.  After such a refusal nothing of the refused set is bound or
+ * cached: a dispatcher that called bind_rules is unbound (its fan-out is
+ * CG_EINVAL until a bind succeeds; a refused patch leaves the bound join as
+ * it was); a refused per-node call leaves no readable per-node result; it
+ * and a refused profile call leave no per-node join cache, so the next
+ * per-node call on any rule set builds its own join; a refused cg_rule_nodes
+ * leaves an earlier per-node result and its cache as they were. */
 
 /* Per-node fire lists: for every node n, the (time, rule) events of the rules
  * scheduled on n (per `mode`), rule-major in ascending rule index, times

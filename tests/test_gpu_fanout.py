@@ -1,7 +1,8 @@
 """The dispatcher's node fan-out (cg_dispatcher_bind_rules / _fanout*) against
 the oracle: after every wake, each node's list must be the oracle's
 Job.Cmds filter of that node (O.node_rules) intersected with the oracle Cron's
-due set (OracleCron.fire), node-major, slots ascending.  Every comparison is
+due set (OracleCron.fire), node-major, slots ascending (join_model.due_filter
+of the oracle's node-major lists).  Every comparison is
 exact and runs with the path forced to FILTER, then DUE, then AUTO."""
 import ctypes as C
 
@@ -11,6 +12,7 @@ import pytest
 import oracle_lib as O
 from common import oracle_parse_all, oracle_zone, random_spec
 from cronsun_amd import _lib, cron, synth
+from join_model import due_filter
 
 pytestmark = pytest.mark.gpu
 
@@ -29,17 +31,6 @@ def eng():
 def node_major(rin, mode):
     """The oracle's node -> rules CSR over every node."""
     return O.node_rules(rin, mode, np.arange(rin.n_nodes, dtype=np.int32))
-
-
-def expected(nm, n_rules, due):
-    """nm restricted to the due slots: (node_off, slots)."""
-    off, rules = nm
-    is_due = np.zeros(n_rules, dtype=bool)
-    d = np.asarray([s for s in due if s < n_rules], dtype=np.int64)
-    is_due[d] = True
-    keep = is_due[rules]
-    rank = np.concatenate([[0], np.cumsum(keep)]).astype(np.int64)
-    return rank[off], rules[keep].astype(np.int32)
 
 
 def check_all_paths(d, exp, what):
@@ -80,7 +71,7 @@ def test_wake_loop_vs_oracle(eng, mode):
         due, _ = d.fire(now)
         odue = oc.fire(e, now)
         assert [int(x) for x in due] == odue, w
-        exp = expected(nm, R, odue)
+        exp = due_filter(*nm, odue)
         check_all_paths(d, exp, w)
         seen_pairs += len(exp[1])
     assert seen_pairs > 0
@@ -131,7 +122,7 @@ def test_tile_edges(eng):
         due, _ = d.fire(e)
         odue = oc.fire(e, e)
         assert [int(x) for x in due] == odue
-        exp = expected(nm, R, odue)
+        exp = due_filter(*nm, odue)
         check_all_paths(d, exp, (w, e - T0))
         sizes.append(len(odue))
         if e == T0 + 60:
@@ -172,14 +163,14 @@ def test_set_and_remove_after_bind(eng):
     assert d.effective == T0 + 15
     due, _ = d.fire(T0 + 15)
     assert due.tolist() == [replaced]
-    exp = expected(nm, R, [replaced])
+    exp = due_filter(*nm, [replaced])
     assert len(exp[1]) > 0
     check_all_paths(d, exp, "replaced")
     # T0 + 20: everything live; the slot past the rule set is due, on no node
     due, _ = d.fire(T0 + 20)
     due = due.tolist()
     assert past in due and replaced in due and removed not in due and len(due) == R
-    exp = expected(nm, R, due)
+    exp = due_filter(*nm, due)
     check_all_paths(d, exp, "all")
     off, slots = d.fanout()
     assert removed not in slots and replaced in slots and slots.max() < R
@@ -210,11 +201,11 @@ def test_rebind(eng):
     d.bind_rules(da, _lib.EXCLUDE_CUMULATIVE)
     due, _ = d.fire(T0 + 10)
     due = due.tolist()
-    check_all_paths(d, expected(node_major(ra, _lib.EXCLUDE_CUMULATIVE), ra.n_rules, due), "a")
+    check_all_paths(d, due_filter(*node_major(ra, _lib.EXCLUDE_CUMULATIVE), due), "a")
     d.bind_rules(db, _lib.EXCLUDE_RULE)
-    check_all_paths(d, expected(node_major(rb, _lib.EXCLUDE_RULE), rb.n_rules, due), "b")
+    check_all_paths(d, due_filter(*node_major(rb, _lib.EXCLUDE_RULE), due), "b")
     due, _ = d.fire(T0 + 20)
-    check_all_paths(d, expected(node_major(rb, _lib.EXCLUDE_RULE), rb.n_rules, due.tolist()), "b2")
+    check_all_paths(d, due_filter(*node_major(rb, _lib.EXCLUDE_RULE), due.tolist()), "b2")
     # a rule set with more rules than the dispatcher has slots is refused
     big = eng.upload_rules(synth.multi_rule_jobs(400, n_nodes=50, seed=83))
     with pytest.raises(_lib.CgError) as err:
@@ -253,7 +244,7 @@ def test_bind_does_not_poison_the_per_node_cache(eng):
     assert np.array_equal(t1_, t2_) and np.array_equal(r1, r2)
     # and the bound join is B's own
     due, _ = d.fire(T0 + 10)
-    check_all_paths(d, expected(node_major(rb, _lib.EXCLUDE_NONE), rb.n_rules, due.tolist()), "b")
+    check_all_paths(d, due_filter(*node_major(rb, _lib.EXCLUDE_NONE), due.tolist()), "b")
     for x in (d, da, db, sp):
         x.free()
 
