@@ -33,6 +33,7 @@ PARSE_STANDARD = 2 | 4 | 8 | 16 | 32 | 128
 EXCLUDE_NONE, EXCLUDE_RULE, EXCLUDE_CUMULATIVE = 0, 1, 2
 NODE_ORDER_RULE, NODE_ORDER_TIME = 0, 1  # cg_set_node_order
 CG_FANOUT_AUTO, CG_FANOUT_FILTER, CG_FANOUT_DUE = 0, 1, 2  # cg_dispatcher_set_fanout_path
+UPCOMING_MAX = 65536  # CG_UPCOMING_MAX: the largest k of cg_dispatcher_upcoming*
 INGEST_OK, INGEST_UNMARSHAL, INGEST_INVALID, INGEST_PANIC, INGEST_REPLACED, INGEST_UNSUPPORTED = range(6)
 
 
@@ -150,6 +151,11 @@ def _declare(L):
         "cg_dispatcher_fanout_range": ([vp, i64, i64, vp], C.c_int),
         "cg_dispatcher_fanout_device": ([vp, P(vp), P(vp), P(i64)], C.c_int),
         "cg_dispatcher_set_fanout_path": ([vp, C.c_int], C.c_int),
+        "cg_dispatcher_upcoming": ([vp, i64, i64, P(i64), P(i64)], C.c_int),
+        "cg_dispatcher_upcoming_node": ([vp, i32, i64, i64, P(i64), P(i64)], C.c_int),
+        "cg_dispatcher_upcoming_copy": ([vp, vp, vp, vp, i64], C.c_int),
+        "cg_dispatcher_upcoming_device": ([vp, P(vp), P(vp), P(vp), P(i64)], C.c_int),
+        "cg_dispatcher_upcoming_times": ([vp, P(C.c_float), C.c_int], C.c_int),
         "cg_expand": ([vp, vp, vp, i64, i64, P(cg_csr)], C.c_int),
         "cg_count": ([vp, vp, vp, i64, i64, vp, P(i64)], C.c_int),
         "cg_expand_device": ([vp, vp, vp, i64, i64, P(i64)], C.c_int),

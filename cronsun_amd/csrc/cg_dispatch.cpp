@@ -63,6 +63,7 @@ void cg_dispatcher::release() {
   idx_dev.release();
   src_dev.release();
   fo.release();
+  up.release();
 }
 
 int cg_dispatcher::ensure_table(int64_t now) {
@@ -196,7 +197,7 @@ int cg_dispatcher_fire(cg_dispatcher* d, int64_t now, int64_t* n_due, int64_t* e
   HIPCHK(hipSetDevice(c->device));
   d->n_due = 0;
   d->wake_valid = true;  // (an empty wake when nothing can fire)
-  d->fo.valid = false;
+  d->fo.valid = d->up.valid = false;
   *n_due = 0;
   *effective = d->effective;
   if (d->effective == CG_ZERO_TIME) return CG_OK;  // nothing can fire: the loop just sleeps
@@ -268,7 +269,7 @@ int cg_dispatcher_set(cg_dispatcher* d, const int64_t* idx, const cg_schedule* s
   std::lock_guard<std::mutex> g(c->mu);
   (void)hipGetLastError();
   HIPCHK(hipSetDevice(c->device));
-  d->wake_valid = d->fo.valid = false;
+  d->wake_valid = d->fo.valid = d->up.valid = false;
   int rc = d->ensure_table(now);
   if (!rc && top > d->n) rc = d->reserve(top);
   if (!rc) rc = d->idx_dev.ensure(k);
@@ -300,7 +301,7 @@ int cg_dispatcher_remove(cg_dispatcher* d, const int64_t* idx, size_t k) {
   std::lock_guard<std::mutex> g(c->mu);
   (void)hipGetLastError();
   HIPCHK(hipSetDevice(c->device));
-  d->wake_valid = d->fo.valid = false;
+  d->wake_valid = d->fo.valid = d->up.valid = false;
   int rc = d->idx_dev.ensure(k);
   if (rc) return rc;
   HIPCHK(hipMemcpyAsync(d->idx_dev.p, idx, k * 8, hipMemcpyHostToDevice, c->st));

@@ -61,6 +61,47 @@ struct DispatchFanout {
   }
 };
 
+// cg_dispatcher_upcoming* (cg_upcoming.hip): the scratch of the select and the
+// last result, in buffers no other entry point touches (a peek leaves the last
+// wake, its due list and its fan-out readable).
+struct DispatchUpcoming {
+  // select: per-block partial histograms (bin-major); their column sums in
+  // mapped, coherent pinned memory k_up_colsum stores straight into (no D2H
+  // copy launch; read once the stream has drained)
+  DBuf<uint32_t> part;
+  unsigned long long* totals_host = nullptr;
+  unsigned long long* totals_dev = nullptr;
+  // compaction: per-tile counts below the cut / inside the cut's class, their scans
+  DBuf<int32_t> cnt_lt, cnt_cl;
+  DBuf<int64_t> base_lt, base_cl;
+  // the selected entries in ascending slot order {key - base, slot}; the sort's
+  // 32-bit key chunks and permutation (ping-pong), its histograms
+  DBuf<unsigned long long> ckey;
+  DBuf<int32_t> cslot, key0, key1, val0, val1, hist;
+  DBuf<int64_t> hist_off;
+  DBuf<char> scan_tmp;
+  // result: n_out entries {slot, Next, Prev} in byTime order
+  DBuf<int32_t> slots;
+  DBuf<int64_t> next, prev;
+  int64_t n_out = 0, n_total = 0;
+  bool valid = false;  // a result is readable (cleared by set / remove / fire / patch / bind)
+  static constexpr int kPhases = 3;  // select, compaction, sort + gather
+  hipEvent_t ev[kPhases + 1] = {};
+  float ms[kPhases] = {0, 0, 0};
+  int passes = 0;  // streaming passes over the candidates of the last call
+  void release() {
+    if (totals_host) (void)hipHostFree(totals_host);
+    totals_host = totals_dev = nullptr;
+    part.release(); cnt_lt.release(); cnt_cl.release(); base_lt.release(); base_cl.release();
+    ckey.release(); cslot.release(); key0.release(); key1.release(); val0.release(); val1.release();
+    hist.release(); hist_off.release(); scan_tmp.release(); slots.release(); next.release(); prev.release();
+    for (hipEvent_t& e : ev)
+      if (e) (void)hipEventDestroy(e), e = nullptr;
+    valid = false;
+    n_out = n_total = 0;
+  }
+};
+
 struct cg_dispatcher {
   cg_ctx* ctx = nullptr;
   cg::ZoneRules zone;
@@ -91,6 +132,7 @@ struct cg_dispatcher {
   DBuf<int64_t> idx_dev;
   DBuf<cg::DSpec> src_dev;
   DispatchFanout fo;
+  DispatchUpcoming up;
 
   void release();
   // the zone table for Next walks from `now`

@@ -461,6 +461,7 @@ int cg_dispatcher_bind_rules(cg_dispatcher* d, const cg_rules* rules, int mode) 
   HIPCHK(hipSetDevice(c->device));
   DispatchFanout& f = d->fo;
   f.bound = f.valid = false;
+  d->up.valid = false;
   // The join is built in the ctx's shared buffers, which the per-node path
   // caches by rule set and mode: drop that cache, then move the result out
   // (rn_nodes is copied before the transpose consumes it).
@@ -500,6 +501,7 @@ int cg_dispatcher_patch_rules(cg_dispatcher* d, const cg_rules* patch, const int
   const RulesStore& st = patch->st;
   const int64_t P = st.n_rules;
   if (P == 0) return CG_OK;
+  d->up.valid = false;  // (a per-node list describes the join this patch edits)
   if (!slot) return cg_fail(CG_EINVAL, "cg_dispatcher_patch_rules: null slots");
   // the patch in ascending slot order (the delta pairs are emitted in it)
   std::vector<SlotOf> ord(size_t(P), SlotOf{0, 0});

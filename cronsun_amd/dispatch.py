@@ -6,6 +6,8 @@ dispatcher (cg_dispatcher_*, Engine.dispatcher).
   Schedule(schedule, job)   add or replace by Job.GetID() (cron.go:125-142)
   DelFunc / DelJob          cron.go:144-164
   Entries()                 snapshot (cron.go:166-174, 296-308), byTime order
+  Upcoming(k, until)        the first k firing entries of Entries(), selected
+                            and sorted in HBM (cg_dispatcher_upcoming)
   Start() / Stop()          the run loop in its own thread (cron.go:181-187, 287-294)
   wake(now)                 one timer wake of run() (cron.go:234-244), returns
                             the entries it ran -- the loop body, callable
@@ -13,6 +15,8 @@ dispatcher (cg_dispatcher_*, Engine.dispatcher).
   ClusterCron(jobset)       every cronnode's Cron as one table: begin(now) /
                             wake(now) -> {node ID: [(Job.ID, Rule.ID), ...]}
                             (cg_dispatcher_bind_rules + cg_dispatcher_fanout);
+                            upcoming(k, until, node_id): what runs next,
+                            cluster-wide or on one node;
                             put_job / del_job / put_group / del_group(.., now)
                             follow the watch stream (node/node.go:143-359)
   ClusterState(jobset)      the live picture behind those edits, host only:
@@ -31,7 +35,7 @@ from typing import Any, Dict, List, Optional
 
 import numpy as np
 
-from ._lib import EXCLUDE_NONE, ZERO_TIME
+from ._lib import EXCLUDE_NONE, NO_PROGRESS_TIME, ZERO_TIME
 from .cron import Parse, Schedule as _Schedule
 
 log = logging.getLogger("cronsun_amd.cron")
@@ -129,6 +133,28 @@ class Cron:
                 n, p = (int(nx[slot]), int(pv[slot])) if self.running else (e.Next, e.Prev)
                 out.append(Entry(ID=e.ID, Schedule=e.Schedule, Next=n, Prev=p, Job=e.Job))
         out.sort(key=lambda x: (x.Next == ZERO_TIME, x.Next))
+        return out
+
+    def Upcoming(self, k, until=None):
+        """Copies of the first k firing entries of Entries() with Next <=
+        until (None: no bound): Next ascending, equal Next in slot order.
+        While running the select and the sort happen in HBM
+        (cg_dispatcher_upcoming), with no snapshot of the table."""
+        if k < 1:
+            raise ValueError("Upcoming: k >= 1")
+        with self._mu:
+            if self.running:
+                slots, nx, pv = self._d.upcoming(k, until)
+                rows = [(int(s), int(n), int(p)) for s, n, p in zip(slots, nx, pv)]
+            else:
+                rows = sorted((e.Next, s, e.Prev) for s, e in enumerate(self._entries)
+                              if e is not None and e.Next not in (ZERO_TIME, NO_PROGRESS_TIME)
+                              and (until is None or e.Next <= until))[:k]
+                rows = [(s, n, p) for n, s, p in rows]
+            out = []
+            for s, n, p in rows:
+                e = self._entries[s]
+                out.append(Entry(ID=e.ID, Schedule=e.Schedule, Next=n, Prev=p, Job=e.Job))
         return out
 
     # ---------------------------------------------------------- run loop
@@ -438,6 +464,28 @@ class ClusterCron:
         for n in np.flatnonzero(np.diff(node_off)):
             out[self._node_id(int(n))] = [self._cmd[int(s)] for s in slots[node_off[n]:node_off[n + 1]]]
         return out
+
+    def upcoming(self, k, until=None, node_id=None):
+        """What runs next: [(next, (Job.ID, Rule.ID)), ...] of the first k
+        firing entries with Next <= until (None: no bound), Next ascending and
+        equal Next in slot order -- cluster-wide, or what cronnode `node_id`'s
+        own Cron.Entries() lists first (KeyError for an unknown node ID).
+        Changes nothing: it may sit between two wakes or inside one."""
+        self._resolve_engine()  # CG_ENODEV without a device
+        if self._d is None:
+            raise RuntimeError("ClusterCron: begin(now) comes before upcoming")
+        node = None
+        if node_id is not None:
+            if self.state is not None:
+                node = self.state._node_index.get(node_id, -1)
+            else:
+                node = self.jobset.node_index(node_id)
+            if node is None or node < 0:
+                raise KeyError(node_id)
+            if node >= getattr(self._d, "_n_nodes", 0):
+                return []  # a node no patch has brought into the join yet
+        slots, nx, _ = self._d.upcoming(k, until, node)
+        return [(int(n), self._cmd[int(s)]) for s, n in zip(slots, nx)]
 
     def _node_id(self, n):
         if self.state is not None:

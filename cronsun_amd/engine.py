@@ -238,6 +238,51 @@ class Dispatcher:
         check(lib().cg_dispatcher_fanout_device(self._h, C.byref(off), C.byref(sl), C.byref(n)))
         return off.value, sl.value, n.value
 
+    # ---------------------------------------------------- what fires next
+    def upcoming_count(self, k, until=None, node=None):
+        """Select the first k entries of Cron.Entries() (byTime order: Next
+        ascending, equal Next by slot) among the firing entries with
+        Next <= until, cluster-wide or over node `node`'s row of the bound
+        join, leaving the list in HBM: (n_out, n_total) -- entries listed,
+        firing entries with Next <= until."""
+        n, tot = C.c_int64(), C.c_int64()
+        u = (1 << 63) - 1 if until is None else int(until)
+        if node is None:
+            check(lib().cg_dispatcher_upcoming(self._h, int(k), u, C.byref(n), C.byref(tot)))
+        else:
+            check(lib().cg_dispatcher_upcoming_node(self._h, int(node), int(k), u, C.byref(n), C.byref(tot)))
+        self.upcoming_total = tot.value
+        return n.value, tot.value
+
+    def upcoming_copy(self, n):
+        """(slots, next, prev) of the last upcoming list, n entries each."""
+        m = max(int(n), 1)
+        sl, nx, pv = np.empty(m, dtype=np.int32), np.empty(m, dtype=np.int64), np.empty(m, dtype=np.int64)
+        check(lib().cg_dispatcher_upcoming_copy(self._h, sl.ctypes.data, nx.ctypes.data, pv.ctypes.data, int(n)))
+        return sl[:n], nx[:n], pv[:n]
+
+    def upcoming(self, k, until=None, node=None):
+        """The next k entries to fire: (slots, next, prev), byTime order.  The
+        number of firing entries with Next <= until is left in
+        self.upcoming_total (larger than len(slots): the list was cut)."""
+        n, _ = self.upcoming_count(k, until, node)
+        return self.upcoming_copy(n)
+
+    def upcoming_device(self):
+        """(slots pointer, next pointer, prev pointer, n) of the last upcoming
+        list in HBM."""
+        sl, nx, pv, n = C.c_void_p(), C.c_void_p(), C.c_void_p(), C.c_int64()
+        check(lib().cg_dispatcher_upcoming_device(self._h, C.byref(sl), C.byref(nx), C.byref(pv), C.byref(n)))
+        return sl.value, nx.value, pv.value, n.value
+
+    def upcoming_ms(self):
+        """Of the last upcoming call: device ms of [select, compaction, sort +
+        gather], and the streaming passes it made over the entries."""
+        buf = (C.c_float * 4)()
+        n = check(lib().cg_dispatcher_upcoming_times(self._h, buf, 4))
+        v = list(buf)[:n]
+        return v[:3], int(v[3])
+
     def snapshot(self):
         """(next, prev, live) per slot."""
         n = len(self)

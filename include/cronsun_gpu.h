@@ -718,6 +718,72 @@ int cg_dispatcher_fanout_device(const cg_dispatcher* d, const int64_t** d_node_o
                                 const int32_t** d_slots, int64_t* n_pairs);
 int cg_dispatcher_set_fanout_path(cg_dispatcher* d, int path);
 
+/* ------------------------------------------- dispatcher: what fires next --- */
+/* The first k entries of Cron.Entries() (node/cron/cron.go:166-174), which
+ * returns the entry list in the order run() keeps it, sort.Sort(byTime):
+ * earliest Next first, zero times last (cron.go:62-79,220).  Selected and
+ * sorted in HBM: no snapshot of the table, no host sort.
+ *
+ * A FIRING entry is a slot whose Next is neither CG_ZERO_TIME nor
+ * CG_NO_PROGRESS_TIME: removed slots, slots skipped by a set past the count,
+ * never-firing specs and stuck slots are not firing, and byTime sorts them
+ * behind every firing entry.
+ *
+ *   cg_dispatcher_upcoming       the first min(k, *n_total) entries of
+ *                             sort.Sort(byTime) over the firing entries with
+ *                             Next <= until (INT64_MAX: no bound): ascending by
+ *                             Next, equal Next values in ascending slot order
+ *                             (one of the orders the reference's unstable sort
+ *                             may give, and the order of the due list).
+ *                             *n_total = firing entries with Next <= until (so
+ *                             the caller sees whether the list was cut),
+ *                             *n_out = entries listed.  CG_EINVAL when k < 1
+ *                             or k > CG_UPCOMING_MAX (a console page; it
+ *                             covers a whole node's entry list at about 9 k
+ *                             entries per node), or when pipelined calls are
+ *                             pending on the ctx (as for bind_rules).  An
+ *                             empty table, a table with no firing entry and an
+ *                             `until` below the effective time give CG_OK and
+ *                             zeros.  With until = the effective time and k >=
+ *                             the count, the slots are the next
+ *                             cg_dispatcher_fire's due list.
+ *   cg_dispatcher_upcoming_node  the same over node `node`'s row of the bound
+ *                             join (what that cronnode's own Cron.Entries()
+ *                             lists first, node/node.go:121-158), under the
+ *                             mode d was bound with and after any patch; slots
+ *                             at or past the bound rule count are on no node.
+ *                             CG_EINVAL when d is unbound or node is outside
+ *                             [0, N).
+ *   cg_dispatcher_upcoming_copy  the columns of the list to the host: slot
+ *                             (i32), Next, Prev (i64), n_out each; any pointer
+ *                             may be NULL.  CG_ECAPACITY naming the required
+ *                             size when cap < n_out.
+ *   cg_dispatcher_upcoming_device  the columns in HBM and n_out.
+ *   cg_dispatcher_upcoming_times  of the last upcoming call: [0..2] device ms
+ *                             of the select, the ordered compaction and the
+ *                             sort + gather (events on the ctx stream), [3]
+ *                             the streaming passes it made over the entries (a
+ *                             count, not a time: at most 11, see
+ *                             cg_upcoming.hip); returns the entries written
+ *                             (at most 4).
+ * The calls change no slot and leave the last wake, its due list and its
+ * fan-out readable (buffers of their own): a peek may sit between
+ * cg_dispatcher_fire and cg_dispatcher_fanout.  The list is readable until
+ * the next upcoming call, or until a set / remove / fire / patch_rules /
+ * bind_rules on d, which change what it describes: _copy and _device then
+ * give CG_EINVAL.  The result is deterministic: the same table gives the same
+ * bytes.  cg_last_kernel_times is not touched. */
+#define CG_UPCOMING_MAX 65536
+int cg_dispatcher_upcoming(cg_dispatcher* d, int64_t k, int64_t until,
+                           int64_t* n_out, int64_t* n_total);
+int cg_dispatcher_upcoming_node(cg_dispatcher* d, int32_t node, int64_t k, int64_t until,
+                                int64_t* n_out, int64_t* n_total);
+int cg_dispatcher_upcoming_copy(const cg_dispatcher* d, int32_t* slots, int64_t* next,
+                                int64_t* prev, int64_t cap);
+int cg_dispatcher_upcoming_device(const cg_dispatcher* d, const int32_t** d_slots,
+                                  const int64_t** d_next, const int64_t** d_prev, int64_t* n);
+int cg_dispatcher_upcoming_times(const cg_dispatcher* d, float* ms, int n);
+
 /* ------------------------------------------- multi-GPU (RCCL over xGMI) --- */
 /* One process (or thread) per MI355X, each with its own cg_ctx; rules shard
  * by contiguous job-ID ranges with no data-path collective (every cronsun

@@ -711,6 +711,56 @@ func (d *Dispatcher) FanoutDevice() (dNodeOff, dSlots uintptr, nPairs int64, err
 	return uintptr(unsafe.Pointer(off)), uintptr(unsafe.Pointer(sl)), int64(n), nil
 }
 
+// UpcomingMax is the largest k of Upcoming / UpcomingNode (CG_UPCOMING_MAX).
+const UpcomingMax = C.CG_UPCOMING_MAX
+
+// Upcoming lists the first k entries of Cron.Entries() (cron.go:166-174: the
+// byTime order of run(), earliest Next first) among the firing entries with
+// Next <= until (the zero time.Time: no bound): per entry its slot, Next and
+// Prev as unix seconds, equal Next values in ascending slot order.  total
+// counts the firing entries with Next <= until, so total > len(slots) means
+// the list was cut.  Nothing is changed and the last Fire / Fanout stay
+// readable.
+func (d *Dispatcher) Upcoming(k int, until time.Time) (slots []int32, next, prev []int64, total int64, err error) {
+	return d.upcoming(-1, k, until)
+}
+
+// UpcomingNode is Upcoming over node `node`'s row of the bound join: what
+// that cronnode's own Cron.Entries() lists first.
+func (d *Dispatcher) UpcomingNode(node int, k int, until time.Time) (slots []int32, next, prev []int64, total int64, err error) {
+	if node < 0 {
+		return nil, nil, nil, 0, errors.New("gpu: UpcomingNode: negative node")
+	}
+	return d.upcoming(node, k, until)
+}
+
+func (d *Dispatcher) upcoming(node, k int, until time.Time) (slots []int32, next, prev []int64, total int64, err error) {
+	defer runtime.KeepAlive(d)
+	u := C.int64_t(1<<63 - 1)
+	if !until.IsZero() {
+		u = C.int64_t(until.Unix())
+	}
+	var n, tot C.int64_t
+	var rc C.int
+	if node < 0 {
+		rc = C.cg_dispatcher_upcoming(d.d, C.int64_t(k), u, &n, &tot)
+	} else {
+		rc = C.cg_dispatcher_upcoming_node(d.d, C.int32_t(node), C.int64_t(k), u, &n, &tot)
+	}
+	if rc != 0 {
+		return nil, nil, nil, 0, lastErr(rc)
+	}
+	slots, next, prev = make([]int32, n), make([]int64, n), make([]int64, n)
+	if n == 0 {
+		return slots, next, prev, int64(tot), nil
+	}
+	if rc := C.cg_dispatcher_upcoming_copy(d.d, (*C.int32_t)(unsafe.Pointer(&slots[0])),
+		(*C.int64_t)(unsafe.Pointer(&next[0])), (*C.int64_t)(unsafe.Pointer(&prev[0])), n); rc != 0 {
+		return nil, nil, nil, 0, lastErr(rc)
+	}
+	return slots, next, prev, int64(tot), nil
+}
+
 // Comm is the library's RCCL communicator (cg_comm_*): one rank per MI355X of
 // a node, each with its own Engine.  Rules shard by job-ID range (every
 // cronsun node filters every job, node/node.go:121-141; a rank here evaluates
