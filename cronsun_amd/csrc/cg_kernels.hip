@@ -315,7 +315,7 @@ constexpr int kScanThreads = 256;
 #endif
 constexpr int kScanPerThread = CG_SCAN_PER_THREAD;
 constexpr int kScanTile = kScanThreads * kScanPerThread;
-constexpr int64_t kScanFuseTiles = 1024;  // up to 4M elements: carries summed per block
+constexpr int64_t kScanFuseTiles = 1024;  // up to 1 048 576 elements (1024-element tiles): carries summed per block
 
 __device__ __forceinline__ int64_t wave_incl_scan(int64_t x) {
   const int lane = threadIdx.x & 63;

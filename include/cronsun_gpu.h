@@ -591,7 +591,11 @@ int cg_expand_per_node_wait(cg_ctx* ctx, int64_t* n_events, int64_t* n_events_al
  *       binning the per-node lists would give
  * width < 1 or n_buckets outside [1, 4096]: CG_EINVAL; n_buckets * width >
  * CG_MAX_HORIZON: CG_ERANGE; a specs count other than the rule set's n_rules:
- * CG_EINVAL (all before any device work).  A rule whose reference loop never
+ * CG_EINVAL (all before any device work).  R * B may exceed 2^32 cells (10M
+ * rules x 1440 buckets is 1.4e10): every index into the matrices is 64-bit,
+ * and the copy accessors below take 64-bit row offsets (cg_profile_copy_rules:
+ * first_rule and count are int64; the byte offset first_rule * B * 4 is formed
+ * in 64 bits).  A rule whose reference loop never
  * ends inside the horizon: CG_ERANGE naming the rule, as cg_expand.  No rule:
  * valid, zero totals.
  * Synchronous, on the ctx's stream.  Like cg_count the calls drain pending

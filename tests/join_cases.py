@@ -94,12 +94,20 @@ def edge_rules(N, R, keys, seed, rules_per_job=(1, 4)):
 
 def nid_rules(N, lists, pause=None):
     """One job per rule, NodeIDs only."""
-    R = len(lists)
     lists = [np.asarray(x, dtype=np.int32) for x in lists]
     nid_off = np.concatenate([[0], np.cumsum([len(x) for x in lists])]).astype(np.int64)
+    return nid_rules_csr(N, nid_off, np.concatenate(lists) if len(lists) and nid_off[-1] else np.zeros(0, np.int32),
+                         pause)
+
+
+def nid_rules_csr(N, nid_off, nids, pause=None):
+    """nid_rules from the lists as one CSR (nid_off [R+1], nids): no Python
+    loop over the rules, for sets of 10^6 rules."""
+    R = len(nid_off) - 1
     zero = np.zeros(R + 1, dtype=np.int64)
     return RulesIn(N, 0, R, R, group_off=np.zeros(1, np.int64), group_nodes=np.zeros(0, np.int32),
                    group_exists=np.zeros(0, np.uint8), rule_job=np.arange(R, dtype=np.int32),
-                   nid_off=nid_off, nids=np.concatenate(lists) if R and nid_off[-1] else np.zeros(0, np.int32),
+                   nid_off=np.ascontiguousarray(nid_off, dtype=np.int64),
+                   nids=np.ascontiguousarray(nids, dtype=np.int32),
                    gid_off=zero, gids=np.zeros(0, np.int32), ex_off=zero, ex=np.zeros(0, np.int32),
                    job_pause=np.zeros(R, np.uint8) if pause is None else np.asarray(pause, np.uint8))

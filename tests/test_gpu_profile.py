@@ -3,19 +3,17 @@
 binned with numpy by (t - t0 - 1) // width, and the oracle's Job.Cmds filter
 (oracle_lib.node_rules) for the per-node matrix.  Exact integer equality
 throughout."""
-import zlib
-
 import numpy as np
 import pytest
 
 import oracle_lib as O
-from common import oracle_parse_all, oracle_zone, product_zone, random_spec
-from cronsun_amd import _lib, cron, synth
-from cronsun_amd.engine import RulesIn
+from common import oracle_parse_all, product_zone
+from cronsun_amd import _lib, cron
+from profile_cases import (T0_UTC, first_transition_2026, oracle_node_matrix, oracle_profile, rule_set, utc_specs,
+                           zone_specs)
 
 pytestmark = pytest.mark.gpu
 
-T0_UTC = 1767571217  # 2026-01-05 00:00:17 UTC
 NY_SPRING, NY_FALL = 1772953200, 1793512800  # 2026-03-08 07:00Z, 2026-11-01 06:00Z
 
 
@@ -23,29 +21,6 @@ NY_SPRING, NY_FALL = 1772953200, 1793512800  # 2026-03-08 07:00Z, 2026-11-01 06:
 def eng():
     from cronsun_amd.engine import Engine
     return Engine(0)
-
-
-def oracle_profile(oscheds, zone, t0, w, B, chunk=128):
-    """rule_counts [R, B] int32 from the oracle's fire lists (a chunk of rules
-    at a time, so a dense 98-day horizon never holds every list at once).
-    Raises O.NonTerminating with indices into oscheds."""
-    R = len(oscheds)
-    out = np.zeros((R, B), dtype=np.int32)
-    t1 = t0 + B * w
-    stuck = []
-    for lo in range(0, R, chunk):
-        hi = min(R, lo + chunk)
-        try:
-            off, times = O.expand_batch(O.sched_array(oscheds[lo:hi]), t0, t1, oracle_zone(zone), threads=8)
-        except O.NonTerminating as e:
-            stuck += [lo + i for i in e.rules]
-            continue
-        rule = np.repeat(np.arange(hi - lo, dtype=np.int64), np.diff(off))
-        cell = rule * B + (times - t0 - 1) // w
-        out[lo:hi] = np.bincount(cell, minlength=(hi - lo) * B).reshape(hi - lo, B)
-    if stuck:
-        raise O.NonTerminating(stuck)
-    return out
 
 
 def check_rules(eng, specs, zone, t0, w, B):
@@ -77,22 +52,6 @@ def check_rules(eng, specs, zone, t0, w, B):
 
 
 # ------------------------------------------------------------ rule matrix --
-EXTRA = ["* * * * * *", "7,30,45 * * * * *", "0 0 0 29 2 *", "0 0 0 30 Feb ?", "@every 7s", "@every 90m",
-         "@every 100h"]
-
-
-def utc_specs(max_every_second=None, stride=1):
-    specs = synth.spec_mix(777, every_second_frac=0.01)[::stride] + EXTRA
-    if max_every_second is not None:  # the others become hourly rules: R stays
-        seen = 0
-        for i, s in enumerate(specs):
-            if s == "* * * * * *":
-                seen += 1
-                if seen > max_every_second:
-                    specs[i] = "@hourly"
-    return specs
-
-
 @pytest.mark.parametrize("w,B", [(1, 130), (7, 1000), (60, 65), (3599, 64), (3600, 48), (86400, 3), (90000, 1),
                                  (604800, 14), (30, 4096)])
 def test_rule_matrix_utc(eng, w, B):
@@ -109,12 +68,6 @@ def test_rule_matrix_utc(eng, w, B):
     check_rules(eng, specs, "UTC", T0_UTC, w, B)
 
 
-def _first_transition_2026(zone):
-    from test_zone import _table
-    when, _ = _table(product_zone(zone), 1767225600, 1798761600)
-    return int(when[1])
-
-
 @pytest.mark.parametrize("w,B", [(1800, 24), (37, 1200)])
 @pytest.mark.parametrize("zone,tau", [("America/New_York", NY_SPRING), ("America/New_York", NY_FALL),
                                       ("America/Havana", None), ("Australia/Lord_Howe", None),
@@ -124,14 +77,8 @@ def test_rule_matrix_zones(eng, zone, tau, w, B):
     transitions (the closed form cut at tau - 1), Havana's walked closed-form
     runs, Lord Howe's 30-minute and Chatham's 45-minute-offset shifts; bucket
     edges inside WALK windows and on tau."""
-    tau = tau or _first_transition_2026(zone)
-    rng = np.random.default_rng(zlib.crc32(("profile" + zone).encode()))
-    specs = []
-    while len(specs) < 200:
-        s = random_spec(rng)
-        if O.parse(s)[1] is None:
-            specs.append(s)
-    specs += ["* * * * * *", "@every 11s"]
+    tau = tau or first_transition_2026(zone)
+    specs = zone_specs(zone)
     check_rules(eng, specs, zone, tau - 6 * 3600 + 17, w, B)
 
 
@@ -154,43 +101,6 @@ def test_apia_skipped_day_is_refused(eng):
 
 
 # --------------------------------------------------------------- per node --
-def edited(rin, seed):
-    """rin with two more nodes -- node N in every rule's NodeIDs (its list
-    spans many chunks), node N+1 in none (a zero row) -- and a tenth of the
-    jobs paused."""
-    N = rin.n_nodes
-    R = rin.n_rules
-    lens = np.diff(rin.nid_off)
-    nid_off = np.concatenate([[0], np.cumsum(lens + 1)]).astype(np.int64)
-    nids = np.empty(int(nid_off[-1]), dtype=np.int32)
-    for r in range(R):
-        a, b = int(rin.nid_off[r]), int(rin.nid_off[r + 1])
-        nids[nid_off[r]:nid_off[r] + (b - a)] = rin.nids[a:b]
-        nids[nid_off[r + 1] - 1] = N
-    pause = np.array(rin.job_pause[:rin.n_jobs], dtype=np.uint8)
-    pause[np.random.default_rng(seed).random(rin.n_jobs) < 0.1] = 1
-    return RulesIn(N + 2, rin.n_groups, R, rin.n_jobs, rule_key=rin.rule_key,
-                   group_off=rin.group_off, group_nodes=rin.group_nodes, group_exists=rin.group_exists,
-                   rule_job=rin.rule_job, nid_off=nid_off, nids=nids, gid_off=rin.gid_off, gids=rin.gids,
-                   ex_off=rin.ex_off, ex=rin.ex, job_pause=pause)
-
-
-_sets = {}
-
-
-def rule_set(name):
-    """(rin, specs, oracle schedules), built once per module."""
-    if name not in _sets:
-        if name == "nodes48":
-            # (groups of 4-24 nodes: the default sizes need more than 48 nodes)
-            rin = edited(synth.rules_for_nodes(3000, n_nodes=48, n_groups=12, group_size=(4, 24)), 5)
-        else:
-            rin = edited(synth.multi_rule_jobs(400, n_nodes=64, key_choices=3), 6)
-        specs = synth.spec_mix(rin.n_rules, seed=4, mix=synth.MIX_LIGHT)
-        _sets[name] = (rin, specs, oracle_parse_all(specs))
-    return _sets[name]
-
-
 _oracle_rules = {}
 
 
@@ -198,14 +108,6 @@ def oracle_rule_matrix(name, w, B):
     if (name, w, B) not in _oracle_rules:
         _oracle_rules[(name, w, B)] = oracle_profile(rule_set(name)[2], "UTC", T0_UTC, w, B)
     return _oracle_rules[(name, w, B)]
-
-
-def oracle_node_matrix(rin, mode, rule_counts):
-    roff, rules = O.node_rules(rin, mode, np.arange(rin.n_nodes))
-    out = np.zeros((rin.n_nodes, rule_counts.shape[1]), dtype=np.int64)
-    for n in range(rin.n_nodes):
-        out[n] = rule_counts[rules[roff[n]:roff[n + 1]]].sum(axis=0, dtype=np.int64)
-    return out, roff
 
 
 @pytest.mark.parametrize("w,B", [(60, 65), (600, 6), (3600, 1), (7, 520)])
