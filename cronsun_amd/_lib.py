@@ -32,6 +32,7 @@ PARSE_STANDARD = 2 | 4 | 8 | 16 | 32 | 128
 
 EXCLUDE_NONE, EXCLUDE_RULE, EXCLUDE_CUMULATIVE = 0, 1, 2
 NODE_ORDER_RULE, NODE_ORDER_TIME = 0, 1  # cg_set_node_order
+PROFILE_STARTS, PROFILE_INFLIGHT = 0, 1  # CG_PROFILE_*: cg_profile_kind
 CG_FANOUT_AUTO, CG_FANOUT_FILTER, CG_FANOUT_DUE = 0, 1, 2  # cg_dispatcher_set_fanout_path
 UPCOMING_MAX = 65536  # CG_UPCOMING_MAX: the largest k of cg_dispatcher_upcoming*
 INGEST_OK, INGEST_UNMARSHAL, INGEST_INVALID, INGEST_PANIC, INGEST_REPLACED, INGEST_UNSUPPORTED = range(6)
@@ -194,6 +195,10 @@ def _declare(L):
         "cg_profile_copy_rules": ([vp, i64, i64, vp], C.c_int),
         "cg_profile_copy_totals": ([vp, vp], C.c_int),
         "cg_profile_copy_nodes": ([vp, i32, i32, vp], C.c_int),
+        "cg_inflight_device": ([vp, vp, vp, i64, i64, i32, vp], C.c_int),
+        "cg_inflight_per_node_device": ([vp, vp, vp, i64, i64, i32, vp, vp, C.c_int], C.c_int),
+        "cg_profile_kind": ([vp, P(C.c_int)], C.c_int),
+        "cg_profile_node_peaks": ([vp, i32, i32, vp, vp], C.c_int),
         "cg_rule_nodes": ([vp, P(cg_rules_in), C.c_int, vp, vp, i64, P(i64)], C.c_int),
         "cg_comm_unique_id": ([vp], C.c_int),
         "cg_comm_init": ([vp, C.c_int, C.c_int, vp, P(vp)], C.c_int),

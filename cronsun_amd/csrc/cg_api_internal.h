@@ -245,7 +245,8 @@ struct cg_ctx {
   // the time-order pass of the last cg_node_result_order_by_time, [13] the
   // last cg_dispatcher_fanout, [14..18] the last profile call (k_profile_rules,
   // k_profile_walk, k_profile_totals, join + transpose when rebuilt, the
-  // node matrix)
+  // node matrix; of an in-flight call k_inflight_rules and k_inflight_walk
+  // in the first two)
   float kt[19] = {0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0};
   // expansion phase timing: 2 = an event between every phase (kt[0..5]);
   // 1 = events around k_write_cf only (kt[3]; the others read -1).  Each
@@ -365,6 +366,13 @@ struct cg_ctx {
   int64_t pf_R = 0;
   int32_t pf_N = 0, pf_B = 0;
   bool pf_valid = false, pf_has_nodes = false;
+  // starts or in flight (CG_PROFILE_*); an in-flight call's durations in
+  // whole seconds [R], uploaded per call; the node matrix's row peaks
+  // (cg_profile_node_peaks: computed on first use after a profile call)
+  int pf_kind = CG_PROFILE_STARTS;
+  DBuf<int64_t> pf_dur, pf_peak;
+  DBuf<int32_t> pf_peak_bucket;
+  bool pf_peaks_valid = false;
   hipEvent_t pfev[6] = {};  // created by the first profile call
 
   void free_all() {
@@ -398,6 +406,7 @@ struct cg_ctx {
     mr_rb.release(); mr_tp.release(); mr_t.release(); mr_r.release();
     pf_rules.release(); pf_chunk_cnt.release(); pf_totals.release(); pf_nodes.release();
     pf_part.release(); pf_chunk_off.release();
+    pf_dur.release(); pf_peak.release(); pf_peak_bucket.release();
     for (hipEvent_t& e : pfev)
       if (e) (void)hipEventDestroy(e), e = nullptr;
   }

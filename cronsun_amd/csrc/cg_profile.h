@@ -70,4 +70,95 @@ CG_HD int32_t profile_cell(const DSpec& sp, const CFRule& c, const Segment* segs
   return n;
 }
 
+// ------------------------------------------------------- in-flight profile --
+// Commands of one rule running at bucket edge e = t0 + (b+1)*w, given an
+// expected run time of d whole seconds (the job's AvgTime in ms, rounded up):
+// the fires t of the rule's expansion over (t0, t1] with e - d < t <= e.
+// Fire times are whole seconds, so that is "started at or before e and not
+// yet finished at e" (t <= e < t + ms/1000) -- hence the rounding up.  (This
+// is not Cmd.lockTtl's `cost`, job.go:213-221, which rounds AvgTime down.)
+// Commands started at or before t0 are unknown and not counted: the lower
+// edge is clipped to t0, and a row ramps up over its first d seconds.  The
+// caller clamps d to t1 - t0, so e - d cannot overflow.
+
+// seconds of a duration in ms, rounded up and clamped to the horizon
+inline int64_t inflight_seconds(int64_t dur_ms, int64_t horizon) {
+  const int64_t d = dur_ms / 1000 + (dur_ms % 1000 != 0);
+  return d < horizon ? d : horizon;
+}
+
+// the closed-form runs' share of the cell at edge e (walked runs: below)
+CG_HD int32_t inflight_cell(const DSpec& sp, const CFRule& c, const Segment* segs, int G,
+                            const int64_t* anchor, const int32_t* count, const uint32_t* dmask,
+                            int64_t t0, int64_t t1, int64_t e, int64_t d) {
+  const int64_t lo = e - d > t0 ? e - d : t0;
+  return profile_cell(sp, c, segs, G, anchor, count, dmask, t1, lo, e);
+}
+
+// Cursor over the walked fires of one rule in ascending order (its walked
+// runs in segment order, each stepped by next_exact from the run's anchor):
+// t is the next fire not yet consumed, INT64_MAX past the last.
+struct WalkCursor {
+  int s = -1;            // run (segment) of t
+  int32_t q = 0, n = 0;  // fires of run s stepped so far, and its count
+  int64_t t = 0;
+};
+
+CG_HD void walk_cursor_next(WalkCursor& k, const DSpec& sp, const ZoneView& z, const Segment* segs, int G,
+                            const int64_t* anchor, const int32_t* count, const uint32_t* dmask, int64_t t1) {
+  while (k.s < G) {
+    if (k.q < k.n) {
+      k.q++;
+      k.t = next_exact(sp, z, k.t, t1);
+      return;
+    }
+    for (k.s++; k.s < G; k.s++)
+      if (count[k.s] != 0 && run_is_walked(segs[k.s], dmask[k.s])) break;
+    if (k.s < G) {
+      k.q = 0;
+      k.n = count[k.s];
+      k.t = anchor[k.s];
+    }
+  }
+  k.t = INT64_MAX;
+}
+
+// The walked runs' share of one rule's row, added to row [B].  A walked fire t
+// is in flight at buckets (t - t0 - 1) / w .. (t + d - 1 - t0) / w - 1; adding
+// 1 to each of them per fire would cost fires x buckets (an every-second rule
+// in an hour-wide WALK window with a long d).  Instead the touched buckets are
+// swept once with two cursors over the fires: at edge e the head has passed
+// the fires <= e and the tail the fires <= e - d, and the cell gains head -
+// tail.  Buckets in which nothing is in flight (between walked runs, beyond
+// the last fire plus d) are skipped: O(fires + buckets touched).
+CG_HD void inflight_walk_row(const DSpec& sp, const ZoneView& z, const Segment* segs, int G,
+                             const int64_t* anchor, const int32_t* count, const uint32_t* dmask,
+                             int64_t t0, int64_t t1, int64_t w, int32_t B, int64_t d, int32_t* row) {
+  if (sp.kind == KIND_EVERY || d <= 0) return;  // closed form in every segment / never in flight
+  WalkCursor head, tail;
+  walk_cursor_next(head, sp, z, segs, G, anchor, count, dmask, t1);
+  if (head.t == INT64_MAX) return;
+  walk_cursor_next(tail, sp, z, segs, G, anchor, count, dmask, t1);
+  int32_t nh = 0, nt = 0;
+  int64_t b = head.t > t0 ? (head.t - t0 - 1) / w : 0;  // (fires lie in (t0, t1]: the row is never left)
+  while (b < B) {
+    const int64_t e = t0 + (b + 1) * w;
+    while (head.t <= e) {
+      nh++;
+      walk_cursor_next(head, sp, z, segs, G, anchor, count, dmask, t1);
+    }
+    while (tail.t <= e - d) {
+      nt++;
+      walk_cursor_next(tail, sp, z, segs, G, anchor, count, dmask, t1);
+    }
+    row[b] += nh - nt;
+    b++;
+    if (nh == nt) {  // nothing in flight: on to the bucket of the next fire
+      if (head.t == INT64_MAX) break;
+      const int64_t nb = (head.t - t0 - 1) / w;
+      if (nb > b) b = nb;
+    }
+  }
+}
+
 }  // namespace cg

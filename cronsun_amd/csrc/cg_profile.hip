@@ -13,6 +13,15 @@
 //                     SpMM): per (chunk of a node's rule list, 64-bucket tile)
 //   k_profile_nodes_reduce  sums the chunk partials of nodes whose list spans
 //                     more than one chunk
+//
+// In-flight profile (cg_inflight_*): commands running at each bucket edge,
+// given a duration per rule.  The same chain with the first two kernels
+// replaced; totals, node matrix and accessors are shared.
+//   k_inflight_rules  k_profile_rules' mapping; cell = fires in (max(t0,
+//                     e_b - d_r), e_b] (cg_profile.h, inflight_cell)
+//   k_inflight_walk   one lane per rule: one two-cursor sweep over the buckets
+//                     its walked fires touch (inflight_walk_row)
+//   k_node_peaks      one wave per node row: (max cell, first bucket with it)
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
@@ -94,6 +103,96 @@ __global__ __launch_bounds__(256) void k_profile_walk(const DSpec* __restrict__ 
         if (t > p.t0 && b < B) row[b] += 1;
       }
     }
+  }
+}
+
+// ------------------------------------------------------ in-flight profile --
+// k_profile_rules' lane mapping; cell (r, b) counts the fires in (max(t0,
+// e - dsec[r]), e] at the bucket's upper edge e (cg_profile.h,
+// inflight_cell).  dsec [R]: whole seconds, clamped to B * w by the host.
+__global__ __launch_bounds__(256) void k_inflight_rules(const DSpec* __restrict__ specs, int64_t R, PlanArgs p,
+                                                         const int64_t* __restrict__ run_anchor,
+                                                         const int32_t* __restrict__ run_count,
+                                                         const uint32_t* __restrict__ run_dmask,
+                                                         const int64_t* __restrict__ dsec, int64_t w, int32_t B,
+                                                         int32_t* __restrict__ out) {
+  extern __shared__ __align__(16) char lds[];
+  PlanView v = stage_plan(p, lds);
+  const int G = p.G;
+  const int64_t cells = R * B, stride = int64_t(gridDim.x) * blockDim.x;
+  int64_t i = blockIdx.x * int64_t(blockDim.x) + threadIdx.x;
+  if (i >= cells) return;
+  const int64_t dr = stride / B;
+  const int32_t db = int32_t(stride - dr * B);
+  int64_t r = i / B;
+  int32_t b = int32_t(i - r * B);
+  for (; i < cells; i += stride) {
+    const DSpec sp = load_spec(specs + r);
+    const CFRule c = cf_rule(sp);
+    const int64_t j0 = r * G;
+    out[i] = inflight_cell(sp, c, v.segs, G, run_anchor + j0, run_count + j0, run_dmask + j0, p.t0, p.t1,
+                           p.t0 + (int64_t(b) + 1) * w, dsec[r]);
+    r += dr;
+    b += db;
+    if (b >= B) {
+      b -= B;
+      r++;
+    }
+  }
+}
+
+// one lane per rule: the walked runs' share, swept once over the touched
+// buckets of the rule's own row (cg_profile.h, inflight_walk_row)
+__global__ __launch_bounds__(256) void k_inflight_walk(const DSpec* __restrict__ specs, int64_t R, PlanArgs p,
+                                                        const int64_t* __restrict__ run_anchor,
+                                                        const int32_t* __restrict__ run_count,
+                                                        const uint32_t* __restrict__ run_dmask,
+                                                        const int64_t* __restrict__ dsec, int64_t w, int32_t B,
+                                                        int32_t* __restrict__ out) {
+  extern __shared__ __align__(16) char lds[];
+  PlanView v = stage_plan(p, lds);
+  const int G = p.G;
+  for (int64_t r = blockIdx.x * int64_t(blockDim.x) + threadIdx.x; r < R; r += int64_t(gridDim.x) * blockDim.x) {
+    const int64_t j0 = r * G;
+    bool walked = false;
+    for (int s = 0; s < G && !walked; s++) walked = run_count[j0 + s] != 0 && run_is_walked(v.segs[s], run_dmask[j0 + s]);
+    if (!walked) continue;
+    const DSpec sp = load_spec(specs + r);
+    inflight_walk_row(sp, v.z, v.segs, G, run_anchor + j0, run_count + j0, run_dmask + j0, p.t0, p.t1, w, B, dsec[r],
+                      out + r * B);
+  }
+}
+
+// one wave per row of the node matrix: (largest cell, first bucket attaining
+// it).  Lanes stride the buckets in ascending order, so a lane keeps the first
+// of equal cells; the wave reduction breaks ties to the smaller bucket.
+__global__ __launch_bounds__(256) void k_node_peaks(const int64_t* __restrict__ nodes, int32_t N, int32_t B,
+                                                     int64_t* __restrict__ peak, int32_t* __restrict__ bucket) {
+  const int32_t lane = threadIdx.x & 63;
+  const int64_t n = int64_t(blockIdx.x) * 4 + (threadIdx.x >> 6);
+  if (n >= N) return;  // a whole wave
+  const int64_t* row = nodes + n * B;
+  int64_t best = -1;  // cells are >= 0, and lane 0 always holds bucket 0
+  int32_t at = 0x7FFFFFFF;
+  for (int32_t b = lane; b < B; b += 64) {
+    const int64_t x = row[b];
+    if (x > best) {
+      best = x;
+      at = b;
+    }
+  }
+  for (int m = 32; m >= 1; m >>= 1) {
+    const int32_t lo = __shfl_xor(int32_t(best), m, 64), hi = __shfl_xor(int32_t(best >> 32), m, 64);
+    const int64_t ob = (int64_t(hi) << 32) | uint32_t(lo);
+    const int32_t oa = __shfl_xor(at, m, 64);
+    if (ob > best || (ob == best && oa < at)) {
+      best = ob;
+      at = oa;
+    }
+  }
+  if (lane == 0) {
+    peak[n] = best;
+    bucket[n] = at;
   }
 }
 
@@ -230,10 +329,14 @@ int ensure_events(cg_ctx* c) {
 
 // count chain + rule matrix + totals, enqueued on the ctx stream (the caller
 // drains it); c->mu held.  pfev[0..3] bracket the three kernels (pfev[3]:
-// the end of the totals, where a per-node call's join starts).
-int profile_rules_enqueue(cg_ctx* c, const cg_specs* s, const cg_zone* z, int64_t t0, int64_t w, int32_t B) {
+// the end of the totals, where a per-node call's join starts).  dsec: null for
+// the start profile, else the in-flight profile's durations (host, [R], whole
+// seconds clamped to B * w), uploaded here and read by this call's kernels only.
+int profile_rules_enqueue(cg_ctx* c, const cg_specs* s, const cg_zone* z, int64_t t0, int64_t w, int32_t B,
+                          const std::vector<int64_t>* dsec) {
   c->pf_valid = false;
   c->pf_has_nodes = false;
+  c->pf_peaks_valid = false;
   int rc;
   bool empty = true;
   if ((rc = sync_count_scan(c, s, z, t0, t0 + int64_t(B) * w, &empty))) return rc;
@@ -252,13 +355,27 @@ int profile_rules_enqueue(cg_ctx* c, const cg_specs* s, const cg_zone* z, int64_
     const unsigned long long stuck = static_cast<unsigned long long>(rs.res_host[1]);
     if (stuck != ~0ULL) return cg_fail(CG_ERANGE, stuck_msg(stuck));
     const size_t lds = plan_lds_bytes(rs.pa);
+    if (dsec) {
+      // (*dsec outlives the stream synchronise that ends the call)
+      if ((rc = c->pf_dur.ensure(size_t(R)))) return rc;
+      HIPCHK(hipMemcpyAsync(c->pf_dur.p, dsec->data(), size_t(R) * 8, hipMemcpyHostToDevice, st));
+    }
     (void)hipEventRecord(c->pfev[0], st);
-    hipLaunchKernelGGL(k_profile_rules, dim3(gridn(R * B, 256, 4096)), dim3(256), lds, st, s->d, R, rs.pa,
-                       rs.run_anchor.p, rs.run_count.p, rs.run_dmask.p, w, B, c->pf_rules.p);
-    (void)hipEventRecord(c->pfev[1], st);
-    if (rs.has_walk())
-      hipLaunchKernelGGL(k_profile_walk, dim3(gridn(R, 256, 256 * 16)), dim3(256), lds, st, s->d, R, rs.pa,
+    if (dsec)
+      hipLaunchKernelGGL(k_inflight_rules, dim3(gridn(R * B, 256, 4096)), dim3(256), lds, st, s->d, R, rs.pa,
+                         rs.run_anchor.p, rs.run_count.p, rs.run_dmask.p, c->pf_dur.p, w, B, c->pf_rules.p);
+    else
+      hipLaunchKernelGGL(k_profile_rules, dim3(gridn(R * B, 256, 4096)), dim3(256), lds, st, s->d, R, rs.pa,
                          rs.run_anchor.p, rs.run_count.p, rs.run_dmask.p, w, B, c->pf_rules.p);
+    (void)hipEventRecord(c->pfev[1], st);
+    if (rs.has_walk()) {
+      if (dsec)
+        hipLaunchKernelGGL(k_inflight_walk, dim3(gridn(R, 256, 256 * 16)), dim3(256), lds, st, s->d, R, rs.pa,
+                           rs.run_anchor.p, rs.run_count.p, rs.run_dmask.p, c->pf_dur.p, w, B, c->pf_rules.p);
+      else
+        hipLaunchKernelGGL(k_profile_walk, dim3(gridn(R, 256, 256 * 16)), dim3(256), lds, st, s->d, R, rs.pa,
+                           rs.run_anchor.p, rs.run_count.p, rs.run_dmask.p, w, B, c->pf_rules.p);
+    }
     (void)hipEventRecord(c->pfev[2], st);
     hipLaunchKernelGGL(k_profile_totals, dim3(gridn(R, kTotalChunk, 1 << 30), (B + 63) / 64), dim3(256), 0, st,
                        c->pf_rules.p, R, B, reinterpret_cast<unsigned long long*>(c->pf_totals.p));
@@ -268,6 +385,7 @@ int profile_rules_enqueue(cg_ctx* c, const cg_specs* s, const cg_zone* z, int64_
   c->pf_R = R;
   c->pf_B = B;
   c->pf_N = 0;
+  c->pf_kind = dsec ? CG_PROFILE_INFLIGHT : CG_PROFILE_STARTS;
   return CG_OK;
 }
 
@@ -282,15 +400,27 @@ void profile_rule_times(cg_ctx* c) {
 
 int profile_no_result() { return cg_fail(CG_EINVAL, "no profile result (the last profile call failed, or none was made)"); }
 
-}  // namespace
+// an in-flight call's durations: ms [R] checked, -> whole seconds rounded up,
+// clamped to the horizon (so INT64_MAX ms is valid and e - d cannot overflow)
+int inflight_durations(const char* what, const cg_specs* s, const int64_t* dur_ms, int64_t horizon,
+                       std::vector<int64_t>* dsec) {
+  const size_t R = s->n;
+  if (R > 0 && !dur_ms) return cg_fail(CG_EINVAL, std::string(what) + ": rule 0: null dur_ms");
+  dsec->resize(R);
+  for (size_t r = 0; r < R; r++) {
+    if (dur_ms[r] < 0)
+      return cg_fail(CG_EINVAL, std::string(what) + ": rule " + std::to_string(r) + ": negative duration");
+    (*dsec)[r] = inflight_seconds(dur_ms[r], horizon);
+  }
+  return CG_OK;
+}
 
-extern "C" {
-
-int cg_profile_device(cg_ctx* c, const cg_specs* s, const cg_zone* z, int64_t t0, int64_t width, int32_t n_buckets) {
-  if (int rc = profile_check_args("cg_profile_device", c, s, z, width, n_buckets)) return rc;
+// the rule-matrix call of either kind (dsec null: starts); arguments checked
+int profile_call(cg_ctx* c, const cg_specs* s, const cg_zone* z, int64_t t0, int64_t width, int32_t n_buckets,
+                 const std::vector<int64_t>* dsec) {
   std::lock_guard<std::mutex> g(c->mu);
   (void)hipGetLastError();  // clear a stale error so launch checks see only their own
-  int rc = profile_rules_enqueue(c, s, z, t0, width, n_buckets);
+  int rc = profile_rules_enqueue(c, s, z, t0, width, n_buckets, dsec);
   if (rc) return rc;
   HIPCHK(hipStreamSynchronize(c->st));
   profile_rule_times(c);
@@ -298,17 +428,21 @@ int cg_profile_device(cg_ctx* c, const cg_specs* s, const cg_zone* z, int64_t t0
   return CG_OK;
 }
 
-int cg_profile_per_node_device(cg_ctx* c, const cg_specs* s, const cg_zone* z, int64_t t0, int64_t width,
-                               int32_t n_buckets, const cg_rules* rules, int mode) {
-  if (int rc = profile_check_args("cg_profile_per_node_device", c, s, z, width, n_buckets)) return rc;
-  if (!rules) return cg_fail(CG_EINVAL, "cg_profile_per_node_device: null");
+int profile_check_node_args(const char* what, const cg_specs* s, const cg_rules* rules, int mode) {
+  if (!rules) return cg_fail(CG_EINVAL, std::string(what) + ": null");
   if (mode < 0 || mode > 2) return cg_fail(CG_EINVAL, "bad exclude mode");
+  if (int64_t(s->n) != rules->st.n_rules) return cg_fail(CG_EINVAL, "specs count != rules n_rules");
+  return CG_OK;
+}
+
+// the per-node call of either kind; arguments checked
+int profile_per_node_call(cg_ctx* c, const cg_specs* s, const cg_zone* z, int64_t t0, int64_t width,
+                          int32_t n_buckets, const cg_rules* rules, int mode, const std::vector<int64_t>* dsec) {
   const RulesStore& in = rules->st;
-  if (int64_t(s->n) != in.n_rules) return cg_fail(CG_EINVAL, "specs count != rules n_rules");
   std::lock_guard<std::mutex> g(c->mu);
   (void)hipGetLastError();
   const int32_t B = n_buckets, N = in.n_nodes;
-  int rc = profile_rules_enqueue(c, s, z, t0, width, B);
+  int rc = profile_rules_enqueue(c, s, z, t0, width, B, dsec);
   if (rc) return rc;
   hipStream_t st = c->st;
   // the rule->node join and its transpose: the per-node path's cache, keyed
@@ -351,6 +485,74 @@ int cg_profile_per_node_device(cg_ctx* c, const cg_specs* s, const cg_zone* z, i
   c->pf_N = N;
   c->pf_has_nodes = true;
   c->pf_valid = true;
+  return CG_OK;
+}
+
+}  // namespace
+
+extern "C" {
+
+int cg_profile_device(cg_ctx* c, const cg_specs* s, const cg_zone* z, int64_t t0, int64_t width, int32_t n_buckets) {
+  if (int rc = profile_check_args("cg_profile_device", c, s, z, width, n_buckets)) return rc;
+  return profile_call(c, s, z, t0, width, n_buckets, nullptr);
+}
+
+int cg_profile_per_node_device(cg_ctx* c, const cg_specs* s, const cg_zone* z, int64_t t0, int64_t width,
+                               int32_t n_buckets, const cg_rules* rules, int mode) {
+  if (int rc = profile_check_args("cg_profile_per_node_device", c, s, z, width, n_buckets)) return rc;
+  if (int rc = profile_check_node_args("cg_profile_per_node_device", s, rules, mode)) return rc;
+  return profile_per_node_call(c, s, z, t0, width, n_buckets, rules, mode, nullptr);
+}
+
+int cg_inflight_device(cg_ctx* c, const cg_specs* s, const cg_zone* z, int64_t t0, int64_t width, int32_t n_buckets,
+                       const int64_t* dur_ms) {
+  std::vector<int64_t> dsec;
+  if (int rc = profile_check_args("cg_inflight_device", c, s, z, width, n_buckets)) return rc;
+  if (int rc = inflight_durations("cg_inflight_device", s, dur_ms, int64_t(n_buckets) * width, &dsec)) return rc;
+  return profile_call(c, s, z, t0, width, n_buckets, &dsec);
+}
+
+int cg_inflight_per_node_device(cg_ctx* c, const cg_specs* s, const cg_zone* z, int64_t t0, int64_t width,
+                                int32_t n_buckets, const int64_t* dur_ms, const cg_rules* rules, int mode) {
+  std::vector<int64_t> dsec;
+  if (int rc = profile_check_args("cg_inflight_per_node_device", c, s, z, width, n_buckets)) return rc;
+  if (int rc = profile_check_node_args("cg_inflight_per_node_device", s, rules, mode)) return rc;
+  if (int rc = inflight_durations("cg_inflight_per_node_device", s, dur_ms, int64_t(n_buckets) * width, &dsec))
+    return rc;
+  return profile_per_node_call(c, s, z, t0, width, n_buckets, rules, mode, &dsec);
+}
+
+int cg_profile_kind(cg_ctx* c, int* kind) {
+  if (!c || !kind) return cg_fail(CG_EINVAL, "cg_profile_kind: null");
+  std::lock_guard<std::mutex> g(c->mu);
+  if (!c->pf_valid) return profile_no_result();
+  *kind = c->pf_kind;
+  return CG_OK;
+}
+
+int cg_profile_node_peaks(cg_ctx* c, int32_t first_node, int32_t count, int64_t* peak, int32_t* bucket) {
+  if (!c || (count > 0 && (!peak || !bucket))) return cg_fail(CG_EINVAL, "cg_profile_node_peaks: null");
+  std::lock_guard<std::mutex> g(c->mu);
+  if (!c->pf_valid) return profile_no_result();
+  if (!c->pf_has_nodes) return cg_fail(CG_EINVAL, "the last profile has no node matrix (no per-node call)");
+  if (first_node < 0 || count < 0 || int64_t(first_node) + count > c->pf_N)
+    return cg_fail(CG_EINVAL, "node range outside the last profile");
+  (void)hipGetLastError();
+  HIPCHK(hipSetDevice(c->device));
+  const int32_t N = c->pf_N;
+  if (!c->pf_peaks_valid && N > 0) {
+    int rc;
+    if ((rc = c->pf_peak.ensure(size_t(N))) || (rc = c->pf_peak_bucket.ensure(size_t(N)))) return rc;
+    hipLaunchKernelGGL(k_node_peaks, dim3(gridn(N, 4, 1 << 30)), dim3(256), 0, c->st, c->pf_nodes.p, N, c->pf_B,
+                       c->pf_peak.p, c->pf_peak_bucket.p);
+    HIPCHK(hipGetLastError());
+    HIPCHK(hipStreamSynchronize(c->st));
+    c->pf_peaks_valid = true;
+  }
+  if (count) {
+    HIPCHK(hipMemcpy(peak, c->pf_peak.p + first_node, size_t(count) * 8, hipMemcpyDeviceToHost));
+    HIPCHK(hipMemcpy(bucket, c->pf_peak_bucket.p + first_node, size_t(count) * 4, hipMemcpyDeviceToHost));
+  }
   return CG_OK;
 }
 

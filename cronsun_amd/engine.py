@@ -14,6 +14,11 @@ seen from Python.  Wraps a cg_ctx (one HIP device + stream + HBM buffers).
                                             fires per (rule, bucket), no lists
   Engine.profile_per_node(specs, loc, t0, width, n_buckets, drules, mode)
                                             fires per (node, bucket)
+  Engine.inflight(specs, loc, t0, width, n_buckets, dur_ms)
+                                            commands running per (rule, bucket edge)
+  Engine.inflight_per_node(specs, loc, t0, width, n_buckets, dur_ms, drules, mode)
+                                            ... per (node, bucket edge)
+  Engine.profile_node_peaks()               per node: largest cell, first bucket with it
 """
 import ctypes as C
 import threading
@@ -827,6 +832,72 @@ class Engine:
         check(lib().cg_profile_per_node_device(self._h, specs._h, self._loc(loc).handle, int(t0), int(width),
                                                int(n_buckets), drules._h, int(mode)))
         return self._profile_tensors()
+
+    # ------------------------------------------------ in-flight profile
+    @staticmethod
+    def _durations(dur_ms, n):
+        d = np.ascontiguousarray(dur_ms, dtype=np.int64)
+        if d.shape != (n,):
+            raise ValueError(f"dur_ms must hold one duration per rule ({n}), got shape {d.shape}")
+        return d
+
+    def inflight(self, specs, loc, t0, width, n_buckets, dur_ms):
+        """Commands running at each bucket edge e_b = t0 + (b+1)*width, per
+        rule (cg_inflight_device): (rule matrix int32 [R, B], totals int64
+        [B]).  dur_ms [R]: expected run time per rule in ms (Job.AvgTime),
+        rounded up to whole seconds d; cell [r, b] counts the fires t of rule
+        r over (t0, t0 + B*width] with e_b - d < t <= e_b.  Commands started
+        at or before t0 are not counted (the rows ramp up)."""
+        sp = self._specs(specs)
+        B = int(n_buckets)
+        d = self._durations(dur_ms, sp.n)
+        check(lib().cg_inflight_device(self._h, sp._h, self._loc(loc).handle, int(t0), int(width), B,
+                                       d.ctypes.data))
+        return self.profile_rules(), self.profile_totals()
+
+    def inflight_per_node(self, specs, loc, t0, width, n_buckets, dur_ms, drules, mode=_lib.EXCLUDE_NONE):
+        """Commands running per node and bucket edge (cg_inflight_per_node_device):
+        int64 [N, B], the in-flight rule matrix summed over the rules each
+        node runs under the exclude mode.  Rule matrix and totals of the same
+        call: profile_rules() / profile_totals(); peaks: profile_node_peaks()."""
+        d = self._durations(dur_ms, specs.n)
+        check(lib().cg_inflight_per_node_device(self._h, specs._h, self._loc(loc).handle, int(t0), int(width),
+                                                int(n_buckets), d.ctypes.data, drules._h, int(mode)))
+        return self.profile_nodes()
+
+    def inflight_device(self, specs, loc, t0, width, n_buckets, dur_ms):
+        """inflight() left in HBM: torch views (rule matrix, totals), valid
+        until the next profile call of either kind."""
+        d = self._durations(dur_ms, specs.n)
+        check(lib().cg_inflight_device(self._h, specs._h, self._loc(loc).handle, int(t0), int(width),
+                                       int(n_buckets), d.ctypes.data))
+        return self._profile_tensors()[:2]
+
+    def inflight_per_node_device(self, specs, loc, t0, width, n_buckets, dur_ms, drules, mode=_lib.EXCLUDE_NONE):
+        """inflight_per_node() left in HBM: torch views (rule matrix, totals,
+        node matrix)."""
+        d = self._durations(dur_ms, specs.n)
+        check(lib().cg_inflight_per_node_device(self._h, specs._h, self._loc(loc).handle, int(t0), int(width),
+                                                int(n_buckets), d.ctypes.data, drules._h, int(mode)))
+        return self._profile_tensors()
+
+    def profile_kind(self):
+        """What the readable profile holds: _lib.PROFILE_STARTS or
+        _lib.PROFILE_INFLIGHT (cg_profile_kind)."""
+        k = C.c_int()
+        check(lib().cg_profile_kind(self._h, C.byref(k)))
+        return k.value
+
+    def profile_node_peaks(self, first=0, count=None):
+        """Per node row [first, first+count) of the last profile's node matrix
+        (of either kind): (peak int64 [count], bucket int32 [count]) -- the
+        largest cell and the first bucket attaining it; (0, 0) for a zero row."""
+        N = self.profile_result_device()[4]
+        count = N - first if count is None else int(count)
+        peak = np.empty(max(count, 1), dtype=np.int64)
+        bucket = np.empty(max(count, 1), dtype=np.int32)
+        check(lib().cg_profile_node_peaks(self._h, int(first), count, peak.ctypes.data, bucket.ctypes.data))
+        return peak[:count], bucket[:count]
 
     def profile_kernel_times(self):
         """ms of the last profile call (cg_last_kernel_times [14..18]):

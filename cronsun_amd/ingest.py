@@ -10,6 +10,8 @@ batch form of GetGroups("") + GetJobs() (group.go:39-63, job.go:339-365).
   js.rules_in()                      the interned CSR for the per-node paths
   js.job_meta()                      Kind, AvgTime, Parallels per job
   js.lock_ttls(now, ...)             Cmd.lockTtl per rule on the GPU
+  js.node_inflight(t0, width, n_buckets)
+                                     commands running per node and bucket edge
 """
 import ctypes as C
 
@@ -17,7 +19,7 @@ import numpy as np
 
 from . import _lib
 from ._lib import check, lib
-from .model import _Interned
+from .model import _Interned, durations_of
 
 
 def _docs_array(docs):
@@ -82,6 +84,28 @@ class EtcdJobSet(_Interned):
         rj = self.rules_in().rule_job[:self.n_rules]
         sp = eng.upload_c(self.schedules_c(), self.n_rules)
         return eng.lock_ttl_batch(sp, loc, now, kind[rj], avg[rj], lock_ttl)
+
+    def rule_durations(self):
+        """(dur_ms int64 [n_rules], rules without an estimate), as JobSet.rule_durations."""
+        avg = self.job_meta()[1]
+        return durations_of(avg[self.rules_in().rule_job[:self.n_rules]])
+
+    def node_inflight(self, t0, width, n_buckets, loc=None, mode=_lib.EXCLUDE_NONE, engine=None):
+        """Commands running per node at each bucket edge, each rule running
+        for its job's AvgTime: ({node ID: int64 [n_buckets]}, rules without an
+        estimate), as JobSet.node_inflight."""
+        from .engine import default_engine
+        eng = engine or default_engine()
+        rin = self.rules_in()
+        dur, missing = self.rule_durations()
+        specs = eng.upload_c(self.schedules_c(), self.n_rules)
+        drules = eng.upload_rules(rin)
+        try:
+            counts = eng.inflight_per_node(specs, loc, t0, width, n_buckets, dur, drules, mode)
+        finally:
+            drules.free()
+            specs.free()
+        return {self.node_id(n): counts[n] for n in range(rin.n_nodes)}, missing
 
 
 __all__ = ["EtcdJobSet"]

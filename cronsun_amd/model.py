@@ -9,6 +9,9 @@ libcronsun_gpu.so (cg_jobset_*).
   JobSet.lock_ttls(now, loc)       Cmd.lockTtl (job.go:194-233) for every rule
   JobSet.node_profile(t0, width, n_buckets)
                                    fires per node and bucket ahead of time
+  JobSet.node_inflight(t0, width, n_buckets)
+                                   commands running per node at each bucket
+                                   edge, by each job's AvgTime
   JobSet(jobs, groups)             all jobs interned at once -> RulesIn for the
                                    GPU per-node expansion (node/node.go:121-158
                                    for every node at once)
@@ -198,11 +201,44 @@ class JobSet(_Interned):
             specs.free()
         return {self.node_id(n): counts[n] for n in range(rin.n_nodes)}
 
+    def rule_durations(self):
+        """(dur_ms int64 [n_rules], rules without an estimate): each rule's
+        job's AvgTime, with AvgTime <= 0 (never run, or the reference's
+        negative values) counted as 0."""
+        return durations_of(np.array([self.jobs[j].AvgTime for j in self.rule_job], dtype=np.int64))
+
+    def node_inflight(self, t0, width, n_buckets, loc=None, mode=_lib.EXCLUDE_NONE, engine=None):
+        """Commands running per node at each bucket edge t0 + (b+1)*width
+        (Engine.inflight_per_node), each rule running for its job's AvgTime
+        (job.go:62): ({node ID: int64 [n_buckets]}, the number of rules that
+        had no estimate and so count as never in flight).  Commands started at
+        or before t0 are not counted; Parallels drops and the KindAlone /
+        KindInterval locks are not modelled."""
+        from .engine import default_engine
+        eng = engine or default_engine()
+        rin = self.rules_in()
+        dur, missing = self.rule_durations()
+        specs = eng.upload(self.schedules())
+        drules = eng.upload_rules(rin)
+        try:
+            counts = eng.inflight_per_node(specs, loc, t0, width, n_buckets, dur, drules, mode)
+        finally:
+            drules.free()
+            specs.free()
+        return {self.node_id(n): counts[n] for n in range(rin.n_nodes)}, missing
+
     def schedules(self):
         """Parsed schedules in rule order (JobRule.Valid on each)."""
         for r in self.rules:
             r.Valid()
         return [r.Schedule for r in self.rules]
+
+
+def durations_of(avg_ms):
+    """Per-rule AvgTime (ms) -> (the in-flight profile's dur_ms, how many rules
+    have no estimate): AvgTime <= 0 counts as 0."""
+    avg = np.asarray(avg_ms, dtype=np.int64)
+    return np.maximum(avg, 0), int((avg <= 0).sum())
 
 
 def rules_in_of(h) -> RulesIn:

@@ -342,7 +342,7 @@ int cg_result_copy_offsets(cg_ctx* ctx, int64_t* host_offsets /* [R+1] */);
  * join, [7] transpose (when the join is rebuilt) + segment records + per-node
  * offsets, [8] per-node write; [12] the last time-order pass; of the last
  * dispatcher wake: [9] scan, [10] due compaction, [11] advance; [13] the last
- * cg_dispatcher_fanout; of the last profile call: [14] rule matrix, [15]
+ * cg_dispatcher_fanout; of the last profile call (starts or in flight): [14] rule matrix, [15]
  * walked runs, [16] totals, [17] join + transpose (when rebuilt), [18] node
  * matrix.  n = entries written. */
 int cg_last_kernel_times(cg_ctx* ctx, float* ms, int n);
@@ -620,6 +620,69 @@ int cg_profile_result_device(cg_ctx* ctx, const int32_t** d_rule_counts,
 int cg_profile_copy_rules(cg_ctx* ctx, int64_t first_rule, int64_t count, int32_t* out /* [count*B] */);
 int cg_profile_copy_totals(cg_ctx* ctx, int64_t* out /* [B] */);
 int cg_profile_copy_nodes(cg_ctx* ctx, int32_t first_node, int32_t count, int64_t* out /* [count*B] */);
+
+/* ------------------------------------------------------ in-flight profile --- */
+/* How many commands are running at each sample instant, per rule, cluster-wide
+ * and on each node: starts alone do not tell whether a node can carry its
+ * schedule (ten jobs that run two hours load it differently from ten that run
+ * 300 ms).  The duration per rule is the caller's estimate, normally the job's
+ * AvgTime (ms; job.go:62, kept up to date by Job.Avg, job.go:581-589, and
+ * already the planning cost of Cmd.lockTtl, job.go:213-221).
+ *
+ * Buckets as above: t1 = t0 + n_buckets * width, bucket edge e_b = t0 +
+ * (b+1)*width.  dur_ms[r] >= 0 is rule r's expected run time in milliseconds;
+ * d_r = dur_ms[r] / 1000 rounded UP, in whole seconds.
+ *   rule_counts[r][b] = #{ fires t of rule r's expansion over (t0, t1] :
+ *                          e_b - d_r < t <= e_b }
+ * Fire times are whole seconds, so this is exactly "started at or before e_b
+ * and not yet finished at e_b" (t <= e_b < t + dur_ms/1000); that is why the
+ * rounding is up.  It is not lockTtl's `cost`, which rounds AvgTime down (an
+ * integer-arithmetic slip of the reference).  The expansion is cg_expand's
+ * (@every anchored at t0; a rule that stops stops; a stuck rule: CG_ERANGE
+ * naming it, before any cell is computed).
+ * Commands started at or before t0 are unknown and NOT counted, so the first
+ * d_r seconds of a row ramp up; for a warm profile start t0 earlier and drop
+ * the leading buckets.
+ *   bucket_totals[b]  the column sums: the cluster-wide in-flight count
+ *   node_counts[n][b] the sum over the rules node n runs under the exclude
+ *                     mode (the start profile's join); every node a rule is
+ *                     scheduled on is counted, as the start profile counts
+ *                     Cmd.Run calls
+ * Not reproduced: Job.Parallels drops (job.limit) and the KindAlone /
+ * KindInterval locks -- a command the reference would not start is counted.
+ * Consequences that hold exactly: dur_ms[r] == 0 gives a zero row; d_r ==
+ * width the start profile's row; d_r == m * width the sliding sum of m start
+ * buckets; d_r >= n_buckets * width the prefix sums of the start row (d_r is
+ * clamped to n_buckets * width, so INT64_MAX ms is valid).  A cell is at most
+ * the horizon in seconds (< 2^31): the rule matrix stays int32, node matrix
+ * and totals int64.
+ *
+ * An in-flight call is a profile call: it writes the same ctx buffers and
+ * replaces the readable profile (cg_profile_result_device and
+ * cg_profile_copy_* serve it unchanged), drains pending pipelined calls, shares
+ * and leaves the per-node join cache, and reports its phases in
+ * cg_last_kernel_times [14..18] with the same meanings.  dur_ms is a host
+ * array [R] owned by the caller, copied to the device inside the call and not
+ * retained.  A NULL dur_ms with R > 0, or a negative entry: CG_EINVAL naming
+ * the first such rule, with the other argument checks, before any device work
+ * (the previous profile stays readable). */
+#define CG_PROFILE_STARTS 0
+#define CG_PROFILE_INFLIGHT 1
+int cg_inflight_device(cg_ctx* ctx, const cg_specs* specs, const cg_zone* z, int64_t t0,
+                       int64_t width, int32_t n_buckets, const int64_t* dur_ms /* host, [R] */);
+int cg_inflight_per_node_device(cg_ctx* ctx, const cg_specs* specs, const cg_zone* z, int64_t t0,
+                                int64_t width, int32_t n_buckets, const int64_t* dur_ms /* host, [R] */,
+                                const cg_rules* rules, int mode);
+/* *kind = CG_PROFILE_STARTS or CG_PROFILE_INFLIGHT: what the readable profile
+ * holds.  CG_EINVAL when no profile is readable. */
+int cg_profile_kind(cg_ctx* ctx, int* kind);
+/* Per node row [first_node, first_node + count) of the last profile's node
+ * matrix (of either kind): its largest cell and the first bucket attaining it;
+ * a zero row gives (0, 0).  Computed on the device on first use after a
+ * profile call and kept until the next.  CG_EINVAL when no profile is readable
+ * or the last one has no node matrix. */
+int cg_profile_node_peaks(cg_ctx* ctx, int32_t first_node, int32_t count, int64_t* peak /* [count] */,
+                          int32_t* bucket /* [count] */);
 
 /* ------------------------------------------- dispatcher node fan-out ---- */
 /* One dispatcher table for a whole cluster: after a wake, which node runs

@@ -483,6 +483,137 @@ func (e *Engine) ProfilePerNode(sp *Specs, z *Zone, t0 time.Time, width time.Dur
 	return nodes, totals, nil
 }
 
+// Kinds of the readable profile (ProfileKind).
+const (
+	ProfileStarts   = C.CG_PROFILE_STARTS
+	ProfileInFlight = C.CG_PROFILE_INFLIGHT
+)
+
+// durations checks one duration per rule and returns the pointer C reads
+// (nil for an empty set; the slice holds no Go pointers).
+func durations(durMs []int64, nRules int) (*C.int64_t, error) {
+	if len(durMs) != nRules {
+		return nil, fmt.Errorf("gpu: %d durations for %d rules", len(durMs), nRules)
+	}
+	if nRules == 0 {
+		return nil, nil
+	}
+	return (*C.int64_t)(unsafe.Pointer(&durMs[0])), nil
+}
+
+// InFlight counts the commands of every rule running at each bucket edge
+// t0 + (b+1)*width, given durMs[r], rule r's expected run time in ms (its
+// job's AvgTime, job.go:62): inFlight[r*nBuckets+b] = the fires t of rule r
+// over (t0, t0 + nBuckets*width] with edge - d < t <= edge, d = durMs[r]/1000
+// rounded up (not lockTtl's cost, which rounds down); totals[b] are the column
+// sums.  Commands started at or before t0 are not counted, so a row ramps up
+// over its first d seconds; Parallels drops and the KindAlone / KindInterval
+// locks are not modelled.  Like the rest of this file it has not been
+// compiled here; tests/native/abi_inflight_c.c runs the same calls from C.
+func (e *Engine) InFlight(sp *Specs, z *Zone, t0 time.Time, width time.Duration, nBuckets int, durMs []int64) (inFlight []int32, totals []int64, err error) {
+	defer runtime.KeepAlive(e)
+	defer runtime.KeepAlive(sp)
+	defer runtime.KeepAlive(z)
+	defer runtime.KeepAlive(durMs)
+	d, err := durations(durMs, sp.n)
+	if err != nil {
+		return nil, nil, err
+	}
+	if rc := C.cg_inflight_device(e.ctx, sp.s, z.z, C.int64_t(t0.Unix()), C.int64_t(width/time.Second),
+		C.int32_t(nBuckets), d); rc != 0 {
+		return nil, nil, lastErr(rc)
+	}
+	return e.profileRules(sp.n, nBuckets)
+}
+
+// InFlightPerNode is InFlight summed per node: node ID -> commands running at
+// each bucket edge over the rules that node runs (ProfilePerNode's join);
+// every node a rule is scheduled on is counted.  totals are InFlight's.
+func (e *Engine) InFlightPerNode(sp *Specs, z *Zone, t0 time.Time, width time.Duration, nBuckets int, durMs []int64, j *Jobset, mode int) (nodes map[string][]int64, totals []int64, err error) {
+	defer runtime.KeepAlive(e)
+	defer runtime.KeepAlive(sp)
+	defer runtime.KeepAlive(z)
+	defer runtime.KeepAlive(j)
+	defer runtime.KeepAlive(durMs)
+	d, err := durations(durMs, sp.n)
+	if err != nil {
+		return nil, nil, err
+	}
+	var rin C.cg_rules_in
+	if rc := C.cg_jobset_rules(j.js, &rin); rc != 0 {
+		return nil, nil, lastErr(rc)
+	}
+	var r *C.cg_rules
+	if rc := C.cg_rules_upload(e.ctx, &rin, &r); rc != 0 {
+		return nil, nil, lastErr(rc)
+	}
+	defer C.cg_rules_free(r) // the node matrix stays in the engine's own buffers
+	if rc := C.cg_inflight_per_node_device(e.ctx, sp.s, z.z, C.int64_t(t0.Unix()), C.int64_t(width/time.Second),
+		C.int32_t(nBuckets), d, r, C.int(mode)); rc != 0 {
+		return nil, nil, lastErr(rc)
+	}
+	nn := int(rin.n_nodes)
+	counts := make([]int64, nn*nBuckets)
+	if len(counts) > 0 {
+		if rc := C.cg_profile_copy_nodes(e.ctx, 0, C.int32_t(nn), (*C.int64_t)(unsafe.Pointer(&counts[0]))); rc != 0 {
+			return nil, nil, lastErr(rc)
+		}
+	}
+	totals = make([]int64, nBuckets)
+	if rc := C.cg_profile_copy_totals(e.ctx, (*C.int64_t)(unsafe.Pointer(&totals[0]))); rc != 0 {
+		return nil, nil, lastErr(rc)
+	}
+	nodes = make(map[string][]int64, nn)
+	for n := 0; n < nn; n++ {
+		nodes[C.GoString(C.cg_jobset_node_id(j.js, C.int32_t(n)))] = counts[n*nBuckets : (n+1)*nBuckets]
+	}
+	return nodes, totals, nil
+}
+
+// ProfileKind reports what the readable profile holds: ProfileStarts or
+// ProfileInFlight.
+func (e *Engine) ProfileKind() (int, error) {
+	defer runtime.KeepAlive(e)
+	var kind C.int
+	if rc := C.cg_profile_kind(e.ctx, &kind); rc != 0 {
+		return 0, lastErr(rc)
+	}
+	return int(kind), nil
+}
+
+// Peak is a node row's largest cell and the first bucket attaining it.
+type Peak struct {
+	Count  int64
+	Bucket int
+}
+
+// NodePeaks returns, per node ID of j, the peak of its row in the node matrix
+// of the last ProfilePerNode or InFlightPerNode call made with j (a node that
+// runs nothing: {0, 0}).
+func (e *Engine) NodePeaks(j *Jobset) (map[string]Peak, error) {
+	defer runtime.KeepAlive(e)
+	defer runtime.KeepAlive(j)
+	var rin C.cg_rules_in
+	if rc := C.cg_jobset_rules(j.js, &rin); rc != 0 {
+		return nil, lastErr(rc)
+	}
+	nn := int(rin.n_nodes)
+	res := make(map[string]Peak, nn)
+	if nn == 0 {
+		return res, nil
+	}
+	peak := make([]int64, nn)
+	bucket := make([]int32, nn)
+	if rc := C.cg_profile_node_peaks(e.ctx, 0, C.int32_t(nn), (*C.int64_t)(unsafe.Pointer(&peak[0])),
+		(*C.int32_t)(unsafe.Pointer(&bucket[0]))); rc != 0 {
+		return nil, lastErr(rc)
+	}
+	for n := 0; n < nn; n++ {
+		res[C.GoString(C.cg_jobset_node_id(j.js, C.int32_t(n)))] = Peak{Count: peak[n], Bucket: int(bucket[n])}
+	}
+	return res, nil
+}
+
 // Dispatcher is Cron.run's entry table in HBM: slot = index into the caller's
 // Entry slice (c.indexes).  The run loop keeps its shape:
 //
