@@ -35,6 +35,7 @@ NODE_ORDER_RULE, NODE_ORDER_TIME = 0, 1  # cg_set_node_order
 PROFILE_STARTS, PROFILE_INFLIGHT = 0, 1  # CG_PROFILE_*: cg_profile_kind
 CG_FANOUT_AUTO, CG_FANOUT_FILTER, CG_FANOUT_DUE = 0, 1, 2  # cg_dispatcher_set_fanout_path
 UPCOMING_MAX = 65536  # CG_UPCOMING_MAX: the largest k of cg_dispatcher_upcoming*
+TOP_RULES_MAX = 64  # CG_TOP_RULES_MAX: the largest k of cg_profile_top_rules_*
 INGEST_OK, INGEST_UNMARSHAL, INGEST_INVALID, INGEST_PANIC, INGEST_REPLACED, INGEST_UNSUPPORTED = range(6)
 
 
@@ -199,6 +200,11 @@ def _declare(L):
         "cg_inflight_per_node_device": ([vp, vp, vp, i64, i64, i32, vp, vp, C.c_int], C.c_int),
         "cg_profile_kind": ([vp, P(C.c_int)], C.c_int),
         "cg_profile_node_peaks": ([vp, i32, i32, vp, vp], C.c_int),
+        "cg_profile_top_rules_nodes": ([vp, i32, vp], C.c_int),
+        "cg_profile_top_rules_bucket": ([vp, i32, i32], C.c_int),
+        "cg_profile_top_rules_copy": ([vp, i32, i32, vp, vp, vp, vp, vp], C.c_int),
+        "cg_profile_top_rules_device": ([vp, P(vp), P(vp), P(vp), P(vp), P(vp), P(i32), P(i32)], C.c_int),
+        "cg_profile_top_rules_times": ([vp, P(C.c_float), C.c_int], C.c_int),
         "cg_rule_nodes": ([vp, P(cg_rules_in), C.c_int, vp, vp, i64, P(i64)], C.c_int),
         "cg_comm_unique_id": ([vp], C.c_int),
         "cg_comm_init": ([vp, C.c_int, C.c_int, vp, P(vp)], C.c_int),

@@ -374,8 +374,27 @@ struct cg_ctx {
   DBuf<int32_t> pf_peak_bucket;
   bool pf_peaks_valid = false;
   hipEvent_t pfev[6] = {};  // created by the first profile call
+  // The node matrix is summed over nt_off / nt_rule, which are the per-node
+  // path's cache and may be rebuilt under a readable profile: nt_gen counts
+  // the rebuilds (transpose_locked, and the dispatcher bind that takes the
+  // buffers), pf_nt_gen / pf_nnz are the transpose of the last per-node profile
+  uint64_t nt_gen = 0, pf_nt_gen = 0;
+  int64_t pf_nnz = 0;
+  // top rules of a bucket (cg_top_rules.hip): the last result -- tr_rows rows
+  // of tr_k (rule, count) columns plus three words per row -- and the split
+  // rows' per-chunk lists (keys, non-zero counts) in buffers of their own
+  DBuf<int32_t> tr_rule, tr_cnt, tr_nlisted, tr_ncontrib, tr_bucket, tr_part_nz;
+  DBuf<unsigned long long> tr_part;
+  int32_t tr_rows = 0, tr_k = 0;
+  bool tr_valid = false;
+  float tr_ms[3] = {0, 0, 0};  // select, merge, chunks (cg_profile_top_rules_times)
+  hipEvent_t trev[3] = {};
 
   void free_all() {
+    tr_rule.release(); tr_cnt.release(); tr_nlisted.release(); tr_ncontrib.release();
+    tr_bucket.release(); tr_part_nz.release(); tr_part.release();
+    for (hipEvent_t& e : trev)
+      if (e) (void)hipEventDestroy(e), e = nullptr;
     for (AsyncSet& a : as) a.release();
     for (PnAsyncSet& a : pns) a.release();
     for (hipEvent_t& e : cs_done)
@@ -485,6 +504,14 @@ bool pn_async_pending(const cg_ctx* c);  // an asynchronous expansion not yet wa
 int upload_rules(const cg_rules_in* in, RulesStore* st, hipStream_t s);
 int rule_nodes_locked(cg_ctx* c, const RulesStore& st, int mode, int64_t* nnz_out);
 int transpose_locked(cg_ctx* c, int64_t nnz, int32_t N);
+// rules of a node's list per chunk of the node-matrix sum and of the top-rules
+// select (pf_chunk_off: the exclusive scan of the nodes' chunk counts; a node
+// without rules still has one chunk)
+constexpr int kNodeChunk = 512;
+// k_node_peaks over the readable profile's node matrix (pf_N > 0 rows) into
+// pf_peak / pf_peak_bucket [pf_N], which the caller has sized, on the ctx
+// stream; the caller sets pf_peaks_valid once the stream has drained
+int profile_node_peaks_enqueue(cg_ctx* c);
 // The transpose's stable LSD passes (k_rs_hist / k_rs_scatter, 8 bits a pass)
 // over n (key, value) pairs with keys < N, ping-ponging between (k0, v0) and
 // (k1, v1); *in_second: the sorted pairs are in (k1, v1).  hist needs

@@ -38,9 +38,8 @@ using namespace cg;
 namespace {
 
 constexpr int kMaxBuckets = 4096;
-// rules of a node's list (k_profile_nodes) / rows of the rule matrix
-// (k_profile_totals) summed by one block per bucket tile
-constexpr int kNodeChunk = 512;
+// rules of a node's list (k_profile_nodes: kNodeChunk, cg_api_internal.h) /
+// rows of the rule matrix (k_profile_totals) summed by one block per bucket tile
 constexpr int kTotalChunk = 4096;
 
 // ------------------------------------------------------------ rule matrix --
@@ -337,6 +336,7 @@ int profile_rules_enqueue(cg_ctx* c, const cg_specs* s, const cg_zone* z, int64_
   c->pf_valid = false;
   c->pf_has_nodes = false;
   c->pf_peaks_valid = false;
+  c->tr_valid = false;  // a top-rules result does not outlive its profile
   int rc;
   bool empty = true;
   if ((rc = sync_count_scan(c, s, z, t0, t0 + int64_t(B) * w, &empty))) return rc;
@@ -483,12 +483,21 @@ int profile_per_node_call(cg_ctx* c, const cg_specs* s, const cg_zone* z, int64_
   if (!cached) (void)hipEventElapsedTime(&c->kt[17], c->pfev[3], c->pfev[4]);  // 0: the cached join was reused
   (void)hipEventElapsedTime(&c->kt[18], c->pfev[4], c->pfev[5]);
   c->pf_N = N;
+  c->pf_nnz = nnz;
+  c->pf_nt_gen = c->nt_gen;  // the transpose the node matrix was summed from
   c->pf_has_nodes = true;
   c->pf_valid = true;
   return CG_OK;
 }
 
 }  // namespace
+
+int profile_node_peaks_enqueue(cg_ctx* c) {
+  hipLaunchKernelGGL(k_node_peaks, dim3(gridn(c->pf_N, 4, 1 << 30)), dim3(256), 0, c->st, c->pf_nodes.p, c->pf_N,
+                     c->pf_B, c->pf_peak.p, c->pf_peak_bucket.p);
+  HIPCHK(hipGetLastError());
+  return CG_OK;
+}
 
 extern "C" {
 
@@ -543,9 +552,7 @@ int cg_profile_node_peaks(cg_ctx* c, int32_t first_node, int32_t count, int64_t*
   if (!c->pf_peaks_valid && N > 0) {
     int rc;
     if ((rc = c->pf_peak.ensure(size_t(N))) || (rc = c->pf_peak_bucket.ensure(size_t(N)))) return rc;
-    hipLaunchKernelGGL(k_node_peaks, dim3(gridn(N, 4, 1 << 30)), dim3(256), 0, c->st, c->pf_nodes.p, N, c->pf_B,
-                       c->pf_peak.p, c->pf_peak_bucket.p);
-    HIPCHK(hipGetLastError());
+    if ((rc = profile_node_peaks_enqueue(c))) return rc;
     HIPCHK(hipStreamSynchronize(c->st));
     c->pf_peaks_valid = true;
   }

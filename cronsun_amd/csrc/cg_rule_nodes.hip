@@ -423,6 +423,7 @@ void launch_node_bounds(hipStream_t st, const uint32_t* keys, int64_t n, int32_t
 int transpose_locked(cg_ctx* c, int64_t nnz, int32_t N) {
   hipStream_t st = c->st;
   int rc;
+  c->nt_gen++;  // whatever was built from the old lists no longer matches them
   if ((rc = c->nt_rule.ensure(std::max<int64_t>(nnz, 1)))) return rc;
   if ((rc = c->pair_node.ensure(std::max<int64_t>(nnz, 1)))) return rc;
   if ((rc = c->nt_off.ensure(N + 1))) return rc;

@@ -19,6 +19,10 @@ seen from Python.  Wraps a cg_ctx (one HIP device + stream + HBM buffers).
   Engine.inflight_per_node(specs, loc, t0, width, n_buckets, dur_ms, drules, mode)
                                             ... per (node, bucket edge)
   Engine.profile_node_peaks()               per node: largest cell, first bucket with it
+  Engine.profile_top_rules(k, buckets=None) per node: the k rules with the largest
+                                            cells of one bucket (default: its peak)
+  Engine.profile_top_rules_bucket(bucket, k)
+                                            the same over all rules, cluster-wide
 """
 import ctypes as C
 import threading
@@ -898,6 +902,61 @@ class Engine:
         bucket = np.empty(max(count, 1), dtype=np.int32)
         check(lib().cg_profile_node_peaks(self._h, int(first), count, peak.ctypes.data, bucket.ctypes.data))
         return peak[:count], bucket[:count]
+
+    # ------------------------------------------------ top rules of a bucket
+    def profile_top_rules_device(self):
+        """Device pointers and shape of the last top-rules result
+        (cg_profile_top_rules_device): (rule, count, n_listed, n_contrib,
+        bucket, rows, k); rule / count are int32 [rows, k], the others int32
+        [rows].  Valid until the next top-rules or profile call."""
+        p = [C.c_void_p() for _ in range(5)]
+        rows, k = C.c_int32(), C.c_int32()
+        check(lib().cg_profile_top_rules_device(self._h, *[C.byref(x) for x in p], C.byref(rows), C.byref(k)))
+        return tuple(x.value for x in p) + (rows.value, k.value)
+
+    def profile_top_rules_copy(self, first=0, count=None):
+        """Rows [first, first+count) of the last top-rules result on the host:
+        (rule [count, k], count [count, k], n_listed, n_contrib, bucket)."""
+        rows, k = self.profile_top_rules_device()[5:]
+        count = rows - first if count is None else int(count)
+        n = max(count, 1)
+        rule, cnt = np.empty((n, k), dtype=np.int32), np.empty((n, k), dtype=np.int32)
+        nl, nc, bk = (np.empty(n, dtype=np.int32) for _ in range(3))
+        check(lib().cg_profile_top_rules_copy(self._h, int(first), count, rule.ctypes.data, cnt.ctypes.data,
+                                              nl.ctypes.data, nc.ctypes.data, bk.ctypes.data))
+        return rule[:count], cnt[:count], nl[:count], nc[:count], bk[:count]
+
+    def profile_top_rules(self, k, buckets=None):
+        """Per node of the last per-node profile (of either kind), the rules it
+        runs with the largest cells in one bucket (cg_profile_top_rules_nodes):
+        (rule int32 [N, k], count int32 [N, k], n_listed [N], n_contrib [N],
+        bucket [N]).  Row n ranks bucket buckets[n], by default the node's peak
+        bucket (profile_node_peaks); its contributors -- rules with a cell > 0
+        there -- are ordered by (count descending, rule index ascending) and
+        cut to k, padded with (-1, 0)."""
+        b = None
+        if buckets is not None:
+            N = self.profile_result_device()[4]
+            b = np.ascontiguousarray(buckets, dtype=np.int32)
+            if b.shape != (N,):
+                raise ValueError(f"buckets must hold one bucket per node ({N}), got shape {b.shape}")
+        check(lib().cg_profile_top_rules_nodes(self._h, int(k), None if b is None or b.size == 0 else b.ctypes.data))
+        return self.profile_top_rules_copy()
+
+    def profile_top_rules_bucket(self, bucket, k):
+        """profile_top_rules for the one cluster-wide row: all rules of the
+        last profile, each once (cg_profile_top_rules_bucket); arrays of one
+        row.  Works after a profile call without a node matrix too."""
+        check(lib().cg_profile_top_rules_bucket(self._h, int(bucket), int(k)))
+        return self.profile_top_rules_copy()
+
+    def profile_top_rules_ms(self):
+        """Of the last top-rules call (cg_profile_top_rules_times): [device ms
+        of the select, of the merge of split rows (0 when none was split), the
+        number of chunks the rows were cut into]."""
+        buf = (C.c_float * 3)()
+        n = check(lib().cg_profile_top_rules_times(self._h, buf, 3))
+        return list(buf)[:n]
 
     def profile_kernel_times(self):
         """ms of the last profile call (cg_last_kernel_times [14..18]):

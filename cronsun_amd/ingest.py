@@ -12,6 +12,8 @@ batch form of GetGroups("") + GetJobs() (group.go:39-63, job.go:339-365).
   js.lock_ttls(now, ...)             Cmd.lockTtl per rule on the GPU
   js.node_inflight(t0, width, n_buckets)
                                      commands running per node and bucket edge
+  js.node_peak_rules(t0, width, n_buckets, k)
+                                     per node: peak, bucket, its top k rules there
 """
 import ctypes as C
 
@@ -19,7 +21,7 @@ import numpy as np
 
 from . import _lib
 from ._lib import check, lib
-from .model import _Interned, durations_of
+from .model import _Interned, durations_of, peak_rules_of
 
 
 def _docs_array(docs):
@@ -106,6 +108,19 @@ class EtcdJobSet(_Interned):
             drules.free()
             specs.free()
         return {self.node_id(n): counts[n] for n in range(rin.n_nodes)}, missing
+
+    def node_peak_rules(self, t0, width, n_buckets, k=10, inflight=False, loc=None, mode=_lib.EXCLUDE_NONE,
+                        engine=None):
+        """Which rules make up each node's peak: {node ID: (peak, bucket,
+        [(job ID, rule ID, count), ...])}, with inflight=True (that, rules
+        without an estimate), as JobSet.node_peak_rules."""
+        from .engine import default_engine
+        eng = engine or default_engine()
+        dur, missing = self.rule_durations() if inflight else (None, 0)
+        res = peak_rules_of(self, eng, eng.upload_c(self.schedules_c(), self.n_rules), self.rules_in(), t0, width,
+                            n_buckets, k, dur, loc, mode, lambda j: self.job_id(j).decode(),
+                            lambda r: self.rule_id(r).decode())
+        return (res, missing) if inflight else res
 
 
 __all__ = ["EtcdJobSet"]

@@ -12,6 +12,9 @@ libcronsun_gpu.so (cg_jobset_*).
   JobSet.node_inflight(t0, width, n_buckets)
                                    commands running per node at each bucket
                                    edge, by each job's AvgTime
+  JobSet.node_peak_rules(t0, width, n_buckets, k)
+                                   per node: its peak, the bucket, and the k
+                                   rules that contribute most to it
   JobSet(jobs, groups)             all jobs interned at once -> RulesIn for the
                                    GPU per-node expansion (node/node.go:121-158
                                    for every node at once)
@@ -227,6 +230,24 @@ class JobSet(_Interned):
             specs.free()
         return {self.node_id(n): counts[n] for n in range(rin.n_nodes)}, missing
 
+    def node_peak_rules(self, t0, width, n_buckets, k=10, inflight=False, loc=None, mode=_lib.EXCLUDE_NONE,
+                        engine=None):
+        """Which rules make up each node's peak: {node ID: (peak, bucket,
+        [(job ID, rule ID, count), ...])} -- the largest cell of the node's
+        row in the profile of node_profile (inflight=True: of node_inflight),
+        the first bucket that reaches it, and the node's rules with a count >
+        0 in that bucket, ordered by (count descending, rule order ascending)
+        and cut to k (at most _lib.TOP_RULES_MAX).  A node that runs nothing
+        gives (0, 0, []).  With inflight=True the durations come from
+        rule_durations() and the result is (that dict, rules without an
+        estimate), as node_inflight."""
+        from .engine import default_engine
+        eng = engine or default_engine()
+        dur, missing = self.rule_durations() if inflight else (None, 0)
+        res = peak_rules_of(self, eng, eng.upload(self.schedules()), self.rules_in(), t0, width, n_buckets, k, dur,
+                            loc, mode, lambda j: self.jobs[j].ID, lambda r: self.rules[r].ID)
+        return (res, missing) if inflight else res
+
     def schedules(self):
         """Parsed schedules in rule order (JobRule.Valid on each)."""
         for r in self.rules:
@@ -239,6 +260,29 @@ def durations_of(avg_ms):
     have no estimate): AvgTime <= 0 counts as 0."""
     avg = np.asarray(avg_ms, dtype=np.int64)
     return np.maximum(avg, 0), int((avg <= 0).sum())
+
+
+def peak_rules_of(js, eng, specs, rin, t0, width, n_buckets, k, dur, loc, mode, job_id, rule_id):
+    """node_peak_rules of a job set: the per-node profile (in flight when dur
+    is given), each node's peak, and its top list at the peak bucket mapped
+    back to (job ID, rule ID, count)."""
+    drules = eng.upload_rules(rin)
+    try:
+        if dur is None:
+            eng.profile_per_node(specs, loc, t0, width, n_buckets, drules, mode)
+        else:
+            eng.inflight_per_node(specs, loc, t0, width, n_buckets, dur, drules, mode)
+        peak, _ = eng.profile_node_peaks()
+        rule, cnt, n_listed, _, bucket = eng.profile_top_rules(k)
+    finally:
+        drules.free()
+        specs.free()
+    out = {}
+    for n in range(rin.n_nodes):
+        top = [(job_id(int(rin.rule_job[r])), rule_id(int(r)), int(c))
+               for r, c in zip(rule[n, :n_listed[n]], cnt[n, :n_listed[n]])]
+        out[js.node_id(n)] = (int(peak[n]), int(bucket[n]), top)
+    return out
 
 
 def rules_in_of(h) -> RulesIn:

@@ -684,6 +684,66 @@ int cg_profile_kind(cg_ctx* ctx, int* kind);
 int cg_profile_node_peaks(cg_ctx* ctx, int32_t first_node, int32_t count, int64_t* peak /* [count] */,
                           int32_t* bucket /* [count] */);
 
+/* ---------------------------------------------- top rules of a bucket ---- */
+/* Which rules make up a cell of the node matrix (or a bucket total): the peaks
+ * say that a node will run 900 commands at 09:00, these calls say which rules
+ * they are, without copying the rule matrix to the host.
+ *
+ * Take the readable profile, of either kind (CG_PROFILE_STARTS or
+ * CG_PROFILE_INFLIGHT), and fix a bucket b.  A contributor of a row is a rule
+ * r of that row with rule_counts[r][b] > 0.  A row's top list is its
+ * contributors ordered by (count descending, rule index ascending) and cut to
+ * the first k.  Per row the result holds
+ *   bucket     i32     the column that was ranked
+ *   n_contrib  i32     contributors of the row
+ *   n_listed   i32     min(k, n_contrib)
+ *   rule[k]    i32     the listed rule indices, then padding -1
+ *   count[k]   i32     the listed rules' cells, then padding 0
+ * Rules with a zero cell are never listed.  The sum of rule_counts[r][b] over
+ * all of a node's rules is node_counts[n][b], so with k >= n_contrib the
+ * listed counts sum to the node-matrix cell.  The result is deterministic:
+ * the same profile gives the same bytes.
+ *
+ * The rows of cg_profile_top_rules_nodes are the nodes of the last per-node
+ * profile, each with the rules it runs under that call's exclude mode (the
+ * node-major transpose the node matrix was summed from).  That transpose is
+ * the per-node path's cache, not the profile's own: a per-node call of any
+ * kind with another rule set or exclude mode, or a dispatcher bind, rebuilds it
+ * under the readable profile.  cg_profile_top_rules_nodes then fails with
+ * CG_EINVAL ("the join the profile was built with has been replaced") rather
+ * than rank against other lists; a per-node call that reuses the cached join
+ * leaves it valid, and cg_profile_top_rules_bucket never depends on it.
+ *
+ * Errors, all raised before any device work, leaving the previous top-rules
+ * result readable: k < 1 or k > CG_TOP_RULES_MAX, a bucket outside [0, B)
+ * (naming the first such node), no readable profile, _nodes after a profile
+ * without a node matrix or with a replaced join, pipelined calls pending:
+ * CG_EINVAL.  _copy / _device without a result or with a row range outside it:
+ * CG_EINVAL.  A result lives in ctx buffers of its own, readable until the
+ * next top-rules call or the next profile call of either kind.  The calls
+ * leave the profile, the peaks, every expansion result and
+ * cg_last_kernel_times as they are. */
+#define CG_TOP_RULES_MAX 64
+/* every node of the last per-node profile (N rows): row n ranks bucket[n]
+ * (host array [N]); bucket == NULL ranks each node's own peak bucket, i.e.
+ * cg_profile_node_peaks' (computed here if not yet) -- a zero row ranks
+ * bucket 0 and lists nothing */
+int cg_profile_top_rules_nodes(cg_ctx* ctx, int32_t k, const int32_t* bucket);
+/* cluster-wide: one row whose rules are all R rules of the profile (each rule
+ * once, as bucket_totals counts them); works after cg_profile_device too */
+int cg_profile_top_rules_bucket(cg_ctx* ctx, int32_t bucket, int32_t k);
+/* rows [first, first+count) of the last top-rules result to the host; any
+ * pointer may be NULL; rule / count are [count][k] row-major with the k of the call */
+int cg_profile_top_rules_copy(cg_ctx* ctx, int32_t first, int32_t count, int32_t* rule, int32_t* cnt,
+                              int32_t* n_listed, int32_t* n_contrib, int32_t* bucket);
+int cg_profile_top_rules_device(cg_ctx* ctx, const int32_t** d_rule, const int32_t** d_cnt,
+                                const int32_t** d_n_listed, const int32_t** d_n_contrib,
+                                const int32_t** d_bucket, int32_t* rows, int32_t* k);
+/* of the last top-rules call: [0] device ms of the select, [1] of the merge of
+ * split rows (0 when none was split), [2] the number of chunks the rows were
+ * cut into (a count, not a time); returns the entries written */
+int cg_profile_top_rules_times(cg_ctx* ctx, float* ms, int n);
+
 /* ------------------------------------------- dispatcher node fan-out ---- */
 /* One dispatcher table for a whole cluster: after a wake, which node runs
  * which of the due entries.  Every cronnode runs its own Cron over its own

@@ -614,6 +614,94 @@ func (e *Engine) NodePeaks(j *Jobset) (map[string]Peak, error) {
 	return res, nil
 }
 
+// TopRulesMax is the largest k of TopRules and TopRulesBucket.
+const TopRulesMax = C.CG_TOP_RULES_MAX
+
+// RuleCount is one entry of a top list: a rule (its index in the Specs, i.e.
+// in Jobset.Schedules) and its cell in the ranked bucket.
+type RuleCount struct {
+	Rule  int32
+	Count int32
+}
+
+// TopList is one row of a top-rules result: the bucket that was ranked, how
+// many of the row's rules have a count > 0 there, and the first k of them by
+// (count descending, rule index ascending).
+type TopList struct {
+	Bucket       int
+	Contributors int
+	Rules        []RuleCount
+}
+
+// topRows copies rows [0, rows) of the readable top-rules result.
+func (e *Engine) topRows(rows, k int) ([]TopList, error) {
+	res := make([]TopList, rows)
+	if rows == 0 {
+		return res, nil
+	}
+	rule := make([]int32, rows*k)
+	cnt := make([]int32, rows*k)
+	listed := make([]int32, rows)
+	contrib := make([]int32, rows)
+	bucket := make([]int32, rows)
+	if rc := C.cg_profile_top_rules_copy(e.ctx, 0, C.int32_t(rows), (*C.int32_t)(unsafe.Pointer(&rule[0])),
+		(*C.int32_t)(unsafe.Pointer(&cnt[0])), (*C.int32_t)(unsafe.Pointer(&listed[0])),
+		(*C.int32_t)(unsafe.Pointer(&contrib[0])), (*C.int32_t)(unsafe.Pointer(&bucket[0]))); rc != 0 {
+		return nil, lastErr(rc)
+	}
+	for n := range res {
+		res[n] = TopList{Bucket: int(bucket[n]), Contributors: int(contrib[n]), Rules: make([]RuleCount, listed[n])}
+		for i := range res[n].Rules {
+			res[n].Rules[i] = RuleCount{Rule: rule[n*k+i], Count: cnt[n*k+i]}
+		}
+	}
+	return res, nil
+}
+
+// TopRules answers "which rules are these?" for every node's peak: per node
+// ID of j, the k rules (k <= TopRulesMax) the node runs with the largest cells
+// in its peak bucket (NodePeaks') of the last ProfilePerNode or
+// InFlightPerNode call made with j.  Only the lists leave the device.  It
+// fails when a per-node call with another job set or exclude mode, or a
+// dispatcher bind, has replaced the join since that profile call: repeat the
+// profile call then.
+func (e *Engine) TopRules(j *Jobset, k int) (map[string]TopList, error) {
+	defer runtime.KeepAlive(e)
+	defer runtime.KeepAlive(j)
+	var rin C.cg_rules_in
+	if rc := C.cg_jobset_rules(j.js, &rin); rc != 0 {
+		return nil, lastErr(rc)
+	}
+	if rc := C.cg_profile_top_rules_nodes(e.ctx, C.int32_t(k), nil); rc != 0 {
+		return nil, lastErr(rc)
+	}
+	nn := int(rin.n_nodes)
+	rows, err := e.topRows(nn, k)
+	if err != nil {
+		return nil, err
+	}
+	res := make(map[string]TopList, nn)
+	for n := 0; n < nn; n++ {
+		res[C.GoString(C.cg_jobset_node_id(j.js, C.int32_t(n)))] = rows[n]
+	}
+	return res, nil
+}
+
+// TopRulesBucket is TopRules for the cluster as a whole: the k rules with the
+// largest cells in one bucket of the last profile of either kind (each rule
+// once, as the totals count them).  It needs no node matrix.
+func (e *Engine) TopRulesBucket(bucket, k int) (TopList, error) {
+	defer runtime.KeepAlive(e)
+	if rc := C.cg_profile_top_rules_bucket(e.ctx, C.int32_t(bucket), C.int32_t(k)); rc != 0 {
+		return TopList{}, lastErr(rc)
+	}
+	rows, err := e.topRows(1, k)
+	if err != nil {
+		return TopList{}, err
+	}
+	return rows[0], nil
+}
+
 // Dispatcher is Cron.run's entry table in HBM: slot = index into the caller's
 // Entry slice (c.indexes).  The run loop keeps its shape:
 //
