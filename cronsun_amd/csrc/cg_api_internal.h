@@ -246,8 +246,9 @@ struct cg_ctx {
   // last cg_dispatcher_fanout, [14..18] the last profile call (k_profile_rules,
   // k_profile_walk, k_profile_totals, join + transpose when rebuilt, the
   // node matrix; of an in-flight call k_inflight_rules and k_inflight_walk
-  // in the first two)
-  float kt[19] = {0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0};
+  // in the first two), [19..20] the last admission profile's own kernels
+  // (k_admit_prepare, k_admit_units; 0 after any other profile call)
+  float kt[21] = {0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0};
   // expansion phase timing: 2 = an event between every phase (kt[0..5]);
   // 1 = events around k_write_cf only (kt[3]; the others read -1).  Each
   // event recorded between two kernels costs 6-12 us of idle GPU on this
@@ -373,7 +374,11 @@ struct cg_ctx {
   DBuf<int64_t> pf_dur, pf_peak;
   DBuf<int32_t> pf_peak_bucket;
   bool pf_peaks_valid = false;
-  hipEvent_t pfev[6] = {};  // created by the first profile call
+  // an admission call's compacted units that can drop (cg::AdmitUnit, 24 B
+  // each) and its per-rule "unit can drop" flags [R], uploaded per call
+  DBuf<char> pf_admit_units;
+  DBuf<uint8_t> pf_admit_flag;
+  hipEvent_t pfev[8] = {};  // created by the first profile call ([6], [7]: around k_admit_units)
   // The node matrix is summed over nt_off / nt_rule, which are the per-node
   // path's cache and may be rebuilt under a readable profile: nt_gen counts
   // the rebuilds (transpose_locked, and the dispatcher bind that takes the
@@ -426,6 +431,7 @@ struct cg_ctx {
     pf_rules.release(); pf_chunk_cnt.release(); pf_totals.release(); pf_nodes.release();
     pf_part.release(); pf_chunk_off.release();
     pf_dur.release(); pf_peak.release(); pf_peak_bucket.release();
+    pf_admit_units.release(); pf_admit_flag.release();
     for (hipEvent_t& e : pfev)
       if (e) (void)hipEventDestroy(e), e = nullptr;
   }

@@ -22,6 +22,15 @@
 //   k_inflight_walk   one lane per rule: one two-cursor sweep over the buckets
 //                     its walked fires touch (inflight_walk_row)
 //   k_node_peaks      one wave per node row: (max cell, first bucket with it)
+//
+// Admission profile (cg_admit_*): the fires Job.limit() would admit, or those it
+// would drop.  The start profile's first two kernels fill the rule matrix, then
+//   k_admit_prepare   one lane per cell: zeroes the rows the kind rewrites
+//                     (ADMITTED: of units that can drop; DROPPED: of the others)
+//   k_admit_units     one lane per unit that can drop: walks the unit's
+//                     admitted fires (cg_admit.h, admit_walk_unit) and adds
+//                     (ADMITTED) or subtracts (DROPPED) 1 in the rule's own row
+// and totals, node matrix and accessors are shared.
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
@@ -30,6 +39,7 @@
 
 #include "../../include/cronsun_gpu.h"
 #include "cg_api_internal.h"
+#include "cg_admit.h"
 #include "cg_profile.h"
 #include "cg_stage.h"
 
@@ -41,6 +51,8 @@ constexpr int kMaxBuckets = 4096;
 // rules of a node's list (k_profile_nodes: kNodeChunk, cg_api_internal.h) /
 // rows of the rule matrix (k_profile_totals) summed by one block per bucket tile
 constexpr int kTotalChunk = 4096;
+static_assert(kAdmitMaxParallels == CG_ADMIT_MAX_PARALLELS, "cg_admit.h and the public header disagree");
+static_assert(sizeof(AdmitUnit) == 24, "AdmitUnit is uploaded as 24-byte records");
 
 // ------------------------------------------------------------ rule matrix --
 __global__ __launch_bounds__(256) void k_profile_rules(const DSpec* __restrict__ specs, int64_t R, PlanArgs p,
@@ -160,6 +172,53 @@ __global__ __launch_bounds__(256) void k_inflight_walk(const DSpec* __restrict__
     inflight_walk_row(sp, v.z, v.segs, G, run_anchor + j0, run_count + j0, run_dmask + j0, p.t0, p.t1, w, B, dsec[r],
                       out + r * B);
   }
+}
+
+// ------------------------------------------------------ admission profile --
+// Rows of the rule matrix a call of this kind rewrites: flag[r] != 0 marks the
+// rules of units that can drop.  ADMITTED (zero_flagged): those rows restart
+// from zero and k_admit_units counts the admitted fires into them; DROPPED:
+// the rows of units that never drop are zero, the others keep their starts
+// for k_admit_units to subtract from.  One lane per cell, 64-bit index.
+__global__ __launch_bounds__(256) void k_admit_prepare(const uint8_t* __restrict__ flag, int64_t R, int32_t B,
+                                                        int zero_flagged, int32_t* __restrict__ out) {
+  const int64_t cells = R * B, stride = int64_t(gridDim.x) * blockDim.x;
+  for (int64_t i = blockIdx.x * int64_t(blockDim.x) + threadIdx.x; i < cells; i += stride)
+    if ((flag[i / B] != 0) == (zero_flagged != 0)) out[i] = 0;
+}
+
+// One lane per unit that can drop (units [U], compacted by the host so waves
+// are dense); a block is one wave.  The lane walks the unit's admitted fires
+// and adds `step` (+1 ADMITTED, -1 DROPPED: start - admitted) to the cell of
+// the firing rule's row -- rows belong to one unit, so plain read-modify-write.
+// The ring of the last P admitted starts and the walked runs' remembered
+// positions (cg_admit.h) live in LDS behind the staged plan, [slot][lane]: a
+// lane's slots are 512 B (256 B) apart, conflict-free at any head.
+constexpr int kAdmitBlock = 64;
+__global__ __launch_bounds__(kAdmitBlock) void k_admit_units(const DSpec* __restrict__ specs, PlanArgs p,
+                                                              const int64_t* __restrict__ run_anchor,
+                                                              const int32_t* __restrict__ run_count,
+                                                              const uint32_t* __restrict__ run_dmask,
+                                                              const AdmitUnit* __restrict__ units, int64_t U,
+                                                              size_t ring_off, int64_t w, int32_t B, int32_t step,
+                                                              int32_t* __restrict__ out) {
+  extern __shared__ __align__(16) char lds[];
+  PlanView v = stage_plan(p, lds);
+  // [ring 16][walk t 8] i64, then [rel 8][s 8][q 8] i32, each [slot][lane]
+  int64_t* ring = reinterpret_cast<int64_t*>(lds + ring_off) + threadIdx.x;
+  int32_t* w32 = reinterpret_cast<int32_t*>(ring - threadIdx.x + (kAdmitMaxParallels + kAdmitWalkSlots) * kAdmitBlock) +
+                 threadIdx.x;
+  const AdmitWalkCache wc{ring + kAdmitMaxParallels * kAdmitBlock, w32, w32 + kAdmitWalkSlots * kAdmitBlock,
+                          w32 + 2 * kAdmitWalkSlots * kAdmitBlock, kAdmitBlock};
+  const int64_t i = blockIdx.x * int64_t(kAdmitBlock) + threadIdx.x;
+  if (i >= U) return;
+  const AdmitUnit u = units[i];
+  const int64_t t0 = p.t0;
+  admit_walk_unit(specs, v.z, v.segs, p.G, run_anchor, run_count, run_dmask, t0, p.t1, u, ring, kAdmitBlock, wc,
+                  [&](int64_t r, int64_t t) {
+                    const int64_t b = (t - t0 - 1) / w;
+                    if (t > t0 && b < B) out[r * B + b] += step;
+                  });
 }
 
 // one wave per row of the node matrix: (largest cell, first bucket attaining
@@ -331,8 +390,17 @@ int ensure_events(cg_ctx* c) {
 // the end of the totals, where a per-node call's join starts).  dsec: null for
 // the start profile, else the in-flight profile's durations (host, [R], whole
 // seconds clamped to B * w), uploaded here and read by this call's kernels only.
+// An admission call's checked arguments: the units that can drop, compacted,
+// and per rule whether its unit is one of them.  Host memory that outlives the
+// stream synchronise that ends the call.
+struct AdmitCall {
+  int what = CG_PROFILE_ADMITTED;
+  std::vector<AdmitUnit> units;
+  std::vector<uint8_t> flag;
+};
+
 int profile_rules_enqueue(cg_ctx* c, const cg_specs* s, const cg_zone* z, int64_t t0, int64_t w, int32_t B,
-                          const std::vector<int64_t>* dsec) {
+                          const std::vector<int64_t>* dsec, const AdmitCall* adm = nullptr) {
   c->pf_valid = false;
   c->pf_has_nodes = false;
   c->pf_peaks_valid = false;
@@ -346,8 +414,8 @@ int profile_rules_enqueue(cg_ctx* c, const cg_specs* s, const cg_zone* z, int64_
     return rc;
   hipStream_t st = c->st;
   HIPCHK(hipMemsetAsync(c->pf_totals.p, 0, size_t(B) * 8, st));
-  for (int i = 14; i < 19; i++) c->kt[i] = 0.f;
-  for (int i = 0; i < 4; i++) (void)hipEventRecord(c->pfev[i], st);
+  for (int i = 14; i < 21; i++) c->kt[i] = 0.f;
+  for (int i : {0, 1, 6, 7, 2, 3}) (void)hipEventRecord(c->pfev[i], st);
   if (!empty) {
     RunSet& rs = c->rs;
     // a rule whose reference loop never ends: refuse before any cell is computed
@@ -376,6 +444,26 @@ int profile_rules_enqueue(cg_ctx* c, const cg_specs* s, const cg_zone* z, int64_
         hipLaunchKernelGGL(k_profile_walk, dim3(gridn(R, 256, 256 * 16)), dim3(256), lds, st, s->d, R, rs.pa,
                            rs.run_anchor.p, rs.run_count.p, rs.run_dmask.p, w, B, c->pf_rules.p);
     }
+    if (adm) {
+      // the start rows are in place: rewrite them on the same stream
+      const int64_t U = int64_t(adm->units.size());
+      const size_t ring_off = align_up(lds, 16), admit_lds = ring_off + size_t(kAdmitBlock) * kAdmitLaneBytes;
+      if (U > 0 && admit_lds > 64 * 1024) return cg_fail(CG_ERANGE, "cg_admit: the plan of this horizon leaves no LDS for the admission ring");
+      if ((rc = c->pf_admit_flag.ensure(size_t(R))) || (rc = c->pf_admit_units.ensure(size_t(std::max<int64_t>(U, 1)) * sizeof(AdmitUnit))))
+        return rc;
+      HIPCHK(hipMemcpyAsync(c->pf_admit_flag.p, adm->flag.data(), size_t(R), hipMemcpyHostToDevice, st));
+      if (U > 0)
+        HIPCHK(hipMemcpyAsync(c->pf_admit_units.p, adm->units.data(), size_t(U) * sizeof(AdmitUnit), hipMemcpyHostToDevice, st));
+      (void)hipEventRecord(c->pfev[6], st);
+      hipLaunchKernelGGL(k_admit_prepare, dim3(gridn(R * B, 256, 4096)), dim3(256), 0, st, c->pf_admit_flag.p, R, B,
+                         adm->what == CG_PROFILE_ADMITTED ? 1 : 0, c->pf_rules.p);
+      (void)hipEventRecord(c->pfev[7], st);
+      if (U > 0)
+        hipLaunchKernelGGL(k_admit_units, dim3(unsigned((U + kAdmitBlock - 1) / kAdmitBlock)), dim3(kAdmitBlock), admit_lds,
+                           st, s->d, rs.pa, rs.run_anchor.p, rs.run_count.p, rs.run_dmask.p,
+                           reinterpret_cast<const AdmitUnit*>(c->pf_admit_units.p), U, ring_off, w, B,
+                           adm->what == CG_PROFILE_ADMITTED ? 1 : -1, c->pf_rules.p);
+    }
     (void)hipEventRecord(c->pfev[2], st);
     hipLaunchKernelGGL(k_profile_totals, dim3(gridn(R, kTotalChunk, 1 << 30), (B + 63) / 64), dim3(256), 0, st,
                        c->pf_rules.p, R, B, reinterpret_cast<unsigned long long*>(c->pf_totals.p));
@@ -385,12 +473,18 @@ int profile_rules_enqueue(cg_ctx* c, const cg_specs* s, const cg_zone* z, int64_
   c->pf_R = R;
   c->pf_B = B;
   c->pf_N = 0;
-  c->pf_kind = dsec ? CG_PROFILE_INFLIGHT : CG_PROFILE_STARTS;
+  c->pf_kind = adm ? adm->what : dsec ? CG_PROFILE_INFLIGHT : CG_PROFILE_STARTS;
   return CG_OK;
 }
 
 void profile_rule_times(cg_ctx* c) {
   for (int i = 0; i < 3; i++) (void)hipEventElapsedTime(&c->kt[14 + i], c->pfev[i], c->pfev[i + 1]);
+  if (c->pf_kind == CG_PROFILE_ADMITTED || c->pf_kind == CG_PROFILE_DROPPED) {
+    // the admission kernels sit between the walked runs and the totals
+    (void)hipEventElapsedTime(&c->kt[15], c->pfev[1], c->pfev[6]);
+    (void)hipEventElapsedTime(&c->kt[19], c->pfev[6], c->pfev[7]);
+    (void)hipEventElapsedTime(&c->kt[20], c->pfev[7], c->pfev[2]);
+  }
   // the count and scan behind it, when the chain recorded their events ([0], [1])
   if (c->phase_timing >= 2 && c->pf_R > 0) {
     (void)hipEventElapsedTime(&c->kt[0], c->ev[0], c->ev[1]);
@@ -417,14 +511,55 @@ int inflight_durations(const char* what, const cg_specs* s, const int64_t* dur_m
 
 // the rule-matrix call of either kind (dsec null: starts); arguments checked
 int profile_call(cg_ctx* c, const cg_specs* s, const cg_zone* z, int64_t t0, int64_t width, int32_t n_buckets,
-                 const std::vector<int64_t>* dsec) {
+                 const std::vector<int64_t>* dsec, const AdmitCall* adm = nullptr) {
   std::lock_guard<std::mutex> g(c->mu);
   (void)hipGetLastError();  // clear a stale error so launch checks see only their own
-  int rc = profile_rules_enqueue(c, s, z, t0, width, n_buckets, dsec);
+  int rc = profile_rules_enqueue(c, s, z, t0, width, n_buckets, dsec, adm);
   if (rc) return rc;
   HIPCHK(hipStreamSynchronize(c->st));
   profile_rule_times(c);
   c->pf_valid = true;
+  return CG_OK;
+}
+
+// An admission call's per-rule arguments -> the units that can drop.  Units
+// are the maximal runs of equal unit[] (NULL: every rule its own); all checks
+// name the first offending rule.
+int admit_units(const char* what_fn, const cg_specs* s, const int64_t* dur_ms, const int64_t* parallels,
+                const int32_t* unit, int what, int64_t horizon, AdmitCall* out) {
+  const std::string fn(what_fn);
+  if (what != CG_PROFILE_ADMITTED && what != CG_PROFILE_DROPPED)
+    return cg_fail(CG_EINVAL, fn + ": what must be CG_PROFILE_ADMITTED or CG_PROFILE_DROPPED");
+  const int64_t R = int64_t(s->n);
+  if (R > 0 && !dur_ms) return cg_fail(CG_EINVAL, fn + ": rule 0: null dur_ms");
+  if (R > 0 && !parallels) return cg_fail(CG_EINVAL, fn + ": rule 0: null parallels");
+  for (int64_t r = 0; r < R; r++) {
+    if (dur_ms[r] < 0) return cg_fail(CG_EINVAL, fn + ": rule " + std::to_string(r) + ": negative duration");
+    if (parallels[r] < 0) return cg_fail(CG_EINVAL, fn + ": rule " + std::to_string(r) + ": negative parallels");
+    if (unit && r > 0 && unit[r] < unit[r - 1])
+      return cg_fail(CG_EINVAL, fn + ": rule " + std::to_string(r) + ": unit decreases");
+  }
+  out->what = what;
+  out->units.clear();
+  out->flag.assign(size_t(R), 0);
+  for (int64_t r0 = 0; r0 < R;) {
+    int64_t r1 = r0 + 1;
+    if (unit)
+      for (; r1 < R && unit[r1] == unit[r0]; r1++)
+        if (dur_ms[r1] != dur_ms[r0] || parallels[r1] != parallels[r0])
+          return cg_fail(CG_EINVAL, fn + ": rule " + std::to_string(r1) + ": dur_ms / parallels differ inside unit " +
+                                        std::to_string(unit[r0]));
+    const int64_t P = parallels[r0], d = inflight_seconds(dur_ms[r0], horizon), k = r1 - r0;
+    if (!admit_never_drops(P, d, k)) {
+      if (P > CG_ADMIT_MAX_PARALLELS)
+        return cg_fail(CG_ERANGE, fn + ": rule " + std::to_string(r0) + ": parallels " + std::to_string(P) +
+                                      " can drop and exceeds CG_ADMIT_MAX_PARALLELS (16)");
+      if (k > INT32_MAX) return cg_fail(CG_ERANGE, fn + ": rule " + std::to_string(r0) + ": unit too long");
+      out->units.push_back(AdmitUnit{r0, d, int32_t(k), int32_t(P)});
+      for (int64_t r = r0; r < r1; r++) out->flag[size_t(r)] = 1;
+    }
+    r0 = r1;
+  }
   return CG_OK;
 }
 
@@ -437,12 +572,13 @@ int profile_check_node_args(const char* what, const cg_specs* s, const cg_rules*
 
 // the per-node call of either kind; arguments checked
 int profile_per_node_call(cg_ctx* c, const cg_specs* s, const cg_zone* z, int64_t t0, int64_t width,
-                          int32_t n_buckets, const cg_rules* rules, int mode, const std::vector<int64_t>* dsec) {
+                          int32_t n_buckets, const cg_rules* rules, int mode, const std::vector<int64_t>* dsec,
+                          const AdmitCall* adm = nullptr) {
   const RulesStore& in = rules->st;
   std::lock_guard<std::mutex> g(c->mu);
   (void)hipGetLastError();
   const int32_t B = n_buckets, N = in.n_nodes;
-  int rc = profile_rules_enqueue(c, s, z, t0, width, B, dsec);
+  int rc = profile_rules_enqueue(c, s, z, t0, width, B, dsec, adm);
   if (rc) return rc;
   hipStream_t st = c->st;
   // the rule->node join and its transpose: the per-node path's cache, keyed
@@ -529,6 +665,27 @@ int cg_inflight_per_node_device(cg_ctx* c, const cg_specs* s, const cg_zone* z, 
   if (int rc = inflight_durations("cg_inflight_per_node_device", s, dur_ms, int64_t(n_buckets) * width, &dsec))
     return rc;
   return profile_per_node_call(c, s, z, t0, width, n_buckets, rules, mode, &dsec);
+}
+
+int cg_admit_device(cg_ctx* c, const cg_specs* s, const cg_zone* z, int64_t t0, int64_t width, int32_t n_buckets,
+                    const int64_t* dur_ms, const int64_t* parallels, const int32_t* unit, int what) {
+  AdmitCall adm;
+  if (int rc = profile_check_args("cg_admit_device", c, s, z, width, n_buckets)) return rc;
+  if (int rc = admit_units("cg_admit_device", s, dur_ms, parallels, unit, what, int64_t(n_buckets) * width, &adm))
+    return rc;
+  return profile_call(c, s, z, t0, width, n_buckets, nullptr, &adm);
+}
+
+int cg_admit_per_node_device(cg_ctx* c, const cg_specs* s, const cg_zone* z, int64_t t0, int64_t width,
+                             int32_t n_buckets, const int64_t* dur_ms, const int64_t* parallels,
+                             const int32_t* unit, int what, const cg_rules* rules, int mode) {
+  AdmitCall adm;
+  if (int rc = profile_check_args("cg_admit_per_node_device", c, s, z, width, n_buckets)) return rc;
+  if (int rc = profile_check_node_args("cg_admit_per_node_device", s, rules, mode)) return rc;
+  if (int rc = admit_units("cg_admit_per_node_device", s, dur_ms, parallels, unit, what, int64_t(n_buckets) * width,
+                           &adm))
+    return rc;
+  return profile_per_node_call(c, s, z, t0, width, n_buckets, rules, mode, nullptr, &adm);
 }
 
 int cg_profile_kind(cg_ctx* c, int* kind) {

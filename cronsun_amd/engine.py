@@ -18,6 +18,10 @@ seen from Python.  Wraps a cg_ctx (one HIP device + stream + HBM buffers).
                                             commands running per (rule, bucket edge)
   Engine.inflight_per_node(specs, loc, t0, width, n_buckets, dur_ms, drules, mode)
                                             ... per (node, bucket edge)
+  Engine.admit(specs, loc, t0, width, n_buckets, dur_ms, parallels, unit, what)
+                                            fires Job.limit() admits / drops per (rule, bucket)
+  Engine.admit_per_node(specs, loc, t0, width, n_buckets, dur_ms, parallels, unit, drules, mode, what)
+                                            ... per (node, bucket)
   Engine.profile_node_peaks()               per node: largest cell, first bucket with it
   Engine.profile_top_rules(k, buckets=None) per node: the k rules with the largest
                                             cells of one bucket (default: its peak)
@@ -885,9 +889,74 @@ class Engine:
                                                 int(n_buckets), d.ctypes.data, drules._h, int(mode)))
         return self._profile_tensors()
 
+    # ------------------------------------------------ admission profile
+    _ADMIT_WHAT = {"admitted": _lib.PROFILE_ADMITTED, "dropped": _lib.PROFILE_DROPPED}
+
+    def _admit_args(self, n, dur_ms, parallels, unit, what):
+        """Checked host arrays of an admission call: (dur_ms, parallels, unit
+        pointer or None, CG_PROFILE_*), plus the arrays to keep alive."""
+        if what not in self._ADMIT_WHAT:
+            raise ValueError(f"what must be 'admitted' or 'dropped', got {what!r}")
+        d = self._durations(dur_ms, n)
+        p = np.ascontiguousarray(parallels, dtype=np.int64)
+        if p.shape != (n,):
+            raise ValueError(f"parallels must hold one limit per rule ({n}), got shape {p.shape}")
+        u = None
+        if unit is not None:
+            u = np.ascontiguousarray(unit, dtype=np.int32)
+            if u.shape != (n,):
+                raise ValueError(f"unit must hold one unit per rule ({n}), got shape {u.shape}")
+        return d, p, u, self._ADMIT_WHAT[what]
+
+    def admit(self, specs, loc, t0, width, n_buckets, dur_ms, parallels, unit=None, what="dropped"):
+        """Fires Job.limit() would admit (what="admitted") or drop
+        (what="dropped") per rule and bucket (cg_admit_device): (rule matrix
+        int32 [R, B], totals int64 [B]).  dur_ms [R]: expected run time in ms
+        (Job.AvgTime), rounded up to whole seconds d; parallels [R]: the job's
+        Parallels after alone(), 0 = unlimited; unit [R] (non-decreasing, or
+        None: every rule alone): rules with equal unit share one limit, and
+        must share dur_ms and parallels.  A unit's fires are taken in (time,
+        rule) order; one is admitted while fewer than parallels admitted
+        fires a of the unit have a + d > t.  Commands started at or before t0
+        are not known, so the first d seconds over-admit."""
+        sp = self._specs(specs)
+        d, p, u, w = self._admit_args(sp.n, dur_ms, parallels, unit, what)
+        check(lib().cg_admit_device(self._h, sp._h, self._loc(loc).handle, int(t0), int(width), int(n_buckets),
+                                    d.ctypes.data, p.ctypes.data, None if u is None else u.ctypes.data, w))
+        return self.profile_rules(), self.profile_totals()
+
+    def admit_per_node(self, specs, loc, t0, width, n_buckets, dur_ms, parallels, unit, drules,
+                       mode=_lib.EXCLUDE_NONE, what="dropped"):
+        """Admitted or dropped fires per node and bucket
+        (cg_admit_per_node_device): int64 [N, B], the admission rule matrix
+        summed over the rules each node runs under the exclude mode -- exact
+        when the rules of a unit run on the same nodes.  Rule matrix, totals,
+        peaks and top rules of the same call: profile_rules() /
+        profile_totals() / profile_node_peaks() / profile_top_rules()."""
+        d, p, u, w = self._admit_args(specs.n, dur_ms, parallels, unit, what)
+        check(lib().cg_admit_per_node_device(self._h, specs._h, self._loc(loc).handle, int(t0), int(width),
+                                             int(n_buckets), d.ctypes.data, p.ctypes.data,
+                                             None if u is None else u.ctypes.data, w, drules._h, int(mode)))
+        return self.profile_nodes()
+
+    def admit_device(self, specs, loc, t0, width, n_buckets, dur_ms, parallels, unit=None, what="dropped"):
+        """admit() left in HBM: torch views (rule matrix, totals), valid until
+        the next profile call of any kind."""
+        d, p, u, w = self._admit_args(specs.n, dur_ms, parallels, unit, what)
+        check(lib().cg_admit_device(self._h, specs._h, self._loc(loc).handle, int(t0), int(width), int(n_buckets),
+                                    d.ctypes.data, p.ctypes.data, None if u is None else u.ctypes.data, w))
+        return self._profile_tensors()[:2]
+
+    def admit_kernel_times(self):
+        """ms of the last admission call's own kernels (cg_last_kernel_times
+        [19..20]): the pass that zeroes the rewritten rows, k_admit_units."""
+        buf = (C.c_float * 21)()
+        check(lib().cg_last_kernel_times(self._h, buf, 21))
+        return list(buf)[19:21]
+
     def profile_kind(self):
-        """What the readable profile holds: _lib.PROFILE_STARTS or
-        _lib.PROFILE_INFLIGHT (cg_profile_kind)."""
+        """What the readable profile holds: _lib.PROFILE_STARTS,
+        PROFILE_INFLIGHT, PROFILE_ADMITTED or PROFILE_DROPPED (cg_profile_kind)."""
         k = C.c_int()
         check(lib().cg_profile_kind(self._h, C.byref(k)))
         return k.value

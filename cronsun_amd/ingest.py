@@ -12,6 +12,8 @@ batch form of GetGroups("") + GetJobs() (group.go:39-63, job.go:339-365).
   js.lock_ttls(now, ...)             Cmd.lockTtl per rule on the GPU
   js.node_inflight(t0, width, n_buckets)
                                      commands running per node and bucket edge
+  js.node_drops(t0, width, n_buckets)
+                                     fires Job.limit() would drop per node and bucket
   js.node_peak_rules(t0, width, n_buckets, k)
                                      per node: peak, bucket, its top k rules there
 """
@@ -21,7 +23,7 @@ import numpy as np
 
 from . import _lib
 from ._lib import check, lib
-from .model import _Interned, durations_of, peak_rules_of
+from .model import _Interned, admission_units, drops_of, durations_of, peak_rules_of
 
 
 def _docs_array(docs):
@@ -91,6 +93,23 @@ class EtcdJobSet(_Interned):
         """(dur_ms int64 [n_rules], rules without an estimate), as JobSet.rule_durations."""
         avg = self.job_meta()[1]
         return durations_of(avg[self.rules_in().rule_job[:self.n_rules]])
+
+    def rule_parallels(self):
+        """int64 [n_rules]: each rule's job's Parallels after alone(), as JobSet.rule_parallels."""
+        par = self.job_meta()[2]
+        return np.maximum(par[self.rules_in().rule_job[:self.n_rules]], 0).astype(np.int64)
+
+    def node_drops(self, t0, width, n_buckets, loc=None, mode=_lib.EXCLUDE_NONE, engine=None, what="dropped"):
+        """Fires Job.limit() would drop per node and bucket: ({node ID: int64
+        [n_buckets]}, the IDs of the jobs that were split), as JobSet.node_drops."""
+        from .engine import default_engine
+        eng = engine or default_engine()
+        rin = self.rules_in()
+        dur, _ = self.rule_durations()
+        unit, split = admission_units(rin, mode)
+        specs = eng.upload_c(self.schedules_c(), self.n_rules)
+        return drops_of(self, eng, specs, rin, t0, width, n_buckets, dur, self.rule_parallels(), unit, loc, mode,
+                        what), [self.job_id(j).decode() for j in split]
 
     def node_inflight(self, t0, width, n_buckets, loc=None, mode=_lib.EXCLUDE_NONE, engine=None):
         """Commands running per node at each bucket edge, each rule running

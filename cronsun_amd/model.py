@@ -12,6 +12,9 @@ libcronsun_gpu.so (cg_jobset_*).
   JobSet.node_inflight(t0, width, n_buckets)
                                    commands running per node at each bucket
                                    edge, by each job's AvgTime
+  JobSet.node_drops(t0, width, n_buckets)
+                                   fires Job.limit() would drop per node and
+                                   bucket, by each job's Parallels and AvgTime
   JobSet.node_peak_rules(t0, width, n_buckets, k)
                                    per node: its peak, the bucket, and the k
                                    rules that contribute most to it
@@ -210,12 +213,43 @@ class JobSet(_Interned):
         negative values) counted as 0."""
         return durations_of(np.array([self.jobs[j].AvgTime for j in self.rule_job], dtype=np.int64))
 
+    def rule_parallels(self):
+        """int64 [n_rules]: each rule's job's Parallels after alone()
+        (job.go:378-387: a KindAlone job runs one instance), negative values
+        counted as 0 (unlimited, as Job.limit's `Parallels > 0` treats them)."""
+        par = [1 if self.jobs[j].Kind == KindAlone else self.jobs[j].Parallels for j in self.rule_job]
+        return np.maximum(np.array(par, dtype=np.int64), 0)
+
+    def node_drops(self, t0, width, n_buckets, loc=None, mode=_lib.EXCLUDE_NONE, engine=None, what="dropped"):
+        """Fires Job.limit() would drop per node and bucket
+        (Engine.admit_per_node; what="admitted": those it lets run), each
+        command running for its job's AvgTime and limited by the job's
+        Parallels after alone(): ({node ID: int64 [n_buckets]}, the IDs of
+        the jobs that were split).  A job whose rules all have the same node
+        membership is one unit: its rules share the limit, as they share the
+        job's Count on a node.  A job whose rules differ in NodeIDs, GroupIDs
+        or (under an exclude mode) ExcludeNodeIDs, or repeat a Cmd key, is
+        split: each of its rules is limited on its own, which over-admits,
+        and its ID is returned.  Commands started at or before t0 are not
+        known (the first AvgTime over-admits), fires of one second are taken
+        in rule order, and the KindAlone / KindInterval locks across nodes
+        are not modelled."""
+        from .engine import default_engine
+        eng = engine or default_engine()
+        rin = self.rules_in()
+        dur, _ = self.rule_durations()
+        unit, split = admission_units(rin, mode)
+        specs = eng.upload(self.schedules())
+        return drops_of(self, eng, specs, rin, t0, width, n_buckets, dur, self.rule_parallels(), unit, loc, mode,
+                        what), [self.jobs[j].ID for j in split]
+
     def node_inflight(self, t0, width, n_buckets, loc=None, mode=_lib.EXCLUDE_NONE, engine=None):
         """Commands running per node at each bucket edge t0 + (b+1)*width
         (Engine.inflight_per_node), each rule running for its job's AvgTime
         (job.go:62): ({node ID: int64 [n_buckets]}, the number of rules that
         had no estimate and so count as never in flight).  Commands started at
-        or before t0 are not counted; Parallels drops and the KindAlone /
+        or before t0 are not counted and every fire is counted: the fires
+        Job.limit() would drop are node_drops', and the KindAlone /
         KindInterval locks are not modelled."""
         from .engine import default_engine
         eng = engine or default_engine()
@@ -260,6 +294,51 @@ def durations_of(avg_ms):
     have no estimate): AvgTime <= 0 counts as 0."""
     avg = np.asarray(avg_ms, dtype=np.int64)
     return np.maximum(avg, 0), int((avg <= 0).sum())
+
+
+def admission_units(rin, mode=_lib.EXCLUDE_NONE):
+    """(unit int32 [R], split job indices) for Engine.admit*: unit[r] is the
+    rule's job index where all rules of the job have the same node membership
+    -- the same interned NodeIDs, GroupIDs and, unless mode is EXCLUDE_NONE,
+    ExcludeNodeIDs, as sets, and no repeated Cmd key -- so every node the job
+    runs on sees all its rules.  The rules of any other job become units of
+    their own (numbered past the job indices) and the job is reported."""
+    R, J = rin.n_rules, rin.n_jobs
+    rule_job = np.asarray(rin.rule_job[:R], dtype=np.int64)
+    if R > 1 and (np.diff(rule_job) < 0).any():
+        raise ValueError("the rules of a job must be contiguous and the jobs in order")
+
+    def members(off, vals, r):
+        return frozenset(np.asarray(vals[int(off[r]):int(off[r + 1])]).tolist())
+    unit = np.zeros(R, dtype=np.int64)
+    split, nxt = [], J
+    cuts = [0] + (np.nonzero(np.diff(rule_job))[0] + 1).tolist() + [R] if R else [0]
+    for a, b in zip(cuts[:-1], cuts[1:]):
+        sig = {(members(rin.nid_off, rin.nids, r), members(rin.gid_off, rin.gids, r),
+                members(rin.ex_off, rin.ex, r) if mode != _lib.EXCLUDE_NONE else None) for r in range(a, b)}
+        keys = None if rin.rule_key is None else np.asarray(rin.rule_key[a:b])
+        if len(sig) == 1 and (keys is None or len(set(keys.tolist())) == b - a):
+            unit[a:b] = rule_job[a]
+        else:
+            split.append(int(rule_job[a]))
+            unit[a:b] = np.arange(nxt, nxt + (b - a))
+            nxt += b - a
+    # units must not decrease along the rules: renumber in order of appearance
+    if R:
+        change = np.concatenate([[0], (np.diff(unit) != 0).astype(np.int64)])
+        unit = np.cumsum(change)
+    return unit.astype(np.int32), split
+
+
+def drops_of(js, eng, specs, rin, t0, width, n_buckets, dur, par, unit, loc, mode, what):
+    """node_drops of a job set: {node ID: int64 [B]} of the per-node admission profile."""
+    drules = eng.upload_rules(rin)
+    try:
+        counts = eng.admit_per_node(specs, loc, t0, width, n_buckets, dur, par, unit, drules, mode, what)
+    finally:
+        drules.free()
+        specs.free()
+    return {js.node_id(n): counts[n] for n in range(rin.n_nodes)}
 
 
 def peak_rules_of(js, eng, specs, rin, t0, width, n_buckets, k, dur, loc, mode, job_id, rule_id):

@@ -648,8 +648,9 @@ int cg_profile_copy_nodes(cg_ctx* ctx, int32_t first_node, int32_t count, int64_
  *                     mode (the start profile's join); every node a rule is
  *                     scheduled on is counted, as the start profile counts
  *                     Cmd.Run calls
- * Not reproduced: Job.Parallels drops (job.limit) and the KindAlone /
- * KindInterval locks -- a command the reference would not start is counted.
+ * Not reproduced: the KindAlone / KindInterval locks -- a command the
+ * reference would not start is counted.  (Job.Parallels drops are the
+ * admission profile's, below; this profile counts every fire.)
  * Consequences that hold exactly: dur_ms[r] == 0 gives a zero row; d_r ==
  * width the start profile's row; d_r == m * width the sliding sum of m start
  * buckets; d_r >= n_buckets * width the prefix sums of the start row (d_r is
@@ -673,8 +674,88 @@ int cg_inflight_device(cg_ctx* ctx, const cg_specs* specs, const cg_zone* z, int
 int cg_inflight_per_node_device(cg_ctx* ctx, const cg_specs* specs, const cg_zone* z, int64_t t0,
                                 int64_t width, int32_t n_buckets, const int64_t* dur_ms /* host, [R] */,
                                 const cg_rules* rules, int mode);
-/* *kind = CG_PROFILE_STARTS or CG_PROFILE_INFLIGHT: what the readable profile
- * holds.  CG_EINVAL when no profile is readable. */
+/* ------------------------------------------------------ admission profile --- */
+/* Which fires the reference would run and which it would drop.  Cmd.Run starts
+ * with Job.limit() (job.go:134-139, 165-187): when Parallels > 0 and that many
+ * instances of the job are still running on the node, the fire is dropped and
+ * j.Fail sends a failure notice.  KindAlone jobs are forced to Parallels = 1
+ * (job.go:378-387).  A job that overruns its own period therefore runs
+ * Parallels copies and fails every other fire; these calls say which, where
+ * and when, ahead of time.
+ *
+ * Buckets, t0, w = width, B = n_buckets <= 4096, t1 = t0 + B*w, the expansion
+ * over (t0, t1], @every anchored at t0 and the stuck-rule failure are the start
+ * profile's.  The failure applies to a stuck rule: the call fails with
+ * CG_ERANGE before any cell is computed.
+ *
+ * Per rule the caller gives three values:
+ *   dur_ms[r] >= 0     d_r is dur_ms[r] rounded up to whole seconds and clamped
+ *                      to B*w, exactly as cg_inflight_* does it
+ *   parallels[r] >= 0  the value 0 means unlimited
+ *   unit[r]            an int32 that does not decrease along r
+ * Rules with equal unit form one unit, a contiguous rule range [u0, u1).  A
+ * unit is the job's Count on one node.  All rules of a unit must carry the
+ * same dur_ms and parallels; otherwise the call returns CG_EINVAL naming the
+ * first rule that differs.  unit == NULL means every rule is its own unit.
+ *
+ * The literal process: take the fires of a unit's rules in (t0, t1] in order
+ * of (time ascending, rule index ascending).  With P = parallels and d = d_r,
+ * a fire at t is ADMITTED iff P == 0, or fewer than P already admitted fires a
+ * of the unit have a + d > t.  Otherwise the fire is DROPPED.  Time is whole
+ * seconds, so a + d > t is exactly a*1000 + dur_ms > t*1000: started and not
+ * yet finished.  A fire at the very second an earlier instance ends is
+ * admitted.  dur_ms == 0 admits everything.
+ *   admitted[r][b] = #admitted fires of rule r in bucket b
+ *   dropped[r][b]  = #dropped fires of rule r in bucket b
+ *   admitted + dropped == the start profile, cell by cell
+ *
+ * Not reproduced:
+ *   - Commands started at or before t0 are unknown.  The first d seconds
+ *     therefore over-admit, which is the in-flight profile's ramp.
+ *   - The reference's counter is racy for fires of the same second
+ *     (job.go:170-171).  Here rule order decides.
+ *   - The etcd locks of KindAlone / KindInterval across nodes are still not
+ *     modelled.  An alone job is limited per node only.
+ *   - Actual run times differ from AvgTime.
+ *
+ * A unit with P == 0, d == 0 or P >= k*d (k its rule count: at most one fire
+ * per rule per second) never drops; its rows are the start profile's.  Any
+ * other unit needs P <= CG_ADMIT_MAX_PARALLELS; a larger P that can still drop
+ * fails the call with CG_ERANGE naming the rule.  (The ring of admitted starts
+ * shares the 64 KiB of LDS with the staged plan: a horizon whose plan exceeds
+ * 46 KiB -- decades -- with a unit that can drop is CG_ERANGE too.)
+ *
+ * `what` is CG_PROFILE_ADMITTED or CG_PROFILE_DROPPED and selects the rule
+ * matrix; cg_profile_kind reports it.  The call is a profile call: it replaces
+ * the readable profile, and bucket totals, the node matrix,
+ * cg_profile_result_device, cg_profile_copy_*, cg_profile_node_peaks and
+ * cg_profile_top_rules_* serve it as they serve the other kinds.  The node
+ * matrix sums the rule rows over the rules each node runs (a rule is counted
+ * on every node it is scheduled on, as before); it is exact when the rules of
+ * a unit run on the same nodes, since every node then sees the same stream.
+ * dur_ms, parallels and unit are host arrays [R] owned by the caller, copied
+ * inside the call and not retained.  A NULL dur_ms or parallels with R > 0, a
+ * negative entry, a decreasing unit, mixed dur_ms / parallels inside a unit
+ * (CG_EINVAL naming the first such rule), `what` out of range (CG_EINVAL) and
+ * the CG_ERANGE above are raised with the other argument checks before any
+ * device work; the previous profile stays readable.
+ * cg_last_kernel_times [14..18] as the start profile's, [19] the pass that
+ * zeroes the rewritten rows, [20] the unit walk (k_admit_units). */
+#define CG_PROFILE_ADMITTED 2
+#define CG_PROFILE_DROPPED 3
+#define CG_ADMIT_MAX_PARALLELS 16
+int cg_admit_device(cg_ctx* ctx, const cg_specs* specs, const cg_zone* z, int64_t t0, int64_t width,
+                    int32_t n_buckets, const int64_t* dur_ms /* host, [R] */,
+                    const int64_t* parallels /* host, [R] */, const int32_t* unit /* host, [R]; may be NULL */,
+                    int what);
+int cg_admit_per_node_device(cg_ctx* ctx, const cg_specs* specs, const cg_zone* z, int64_t t0, int64_t width,
+                             int32_t n_buckets, const int64_t* dur_ms /* host, [R] */,
+                             const int64_t* parallels /* host, [R] */,
+                             const int32_t* unit /* host, [R]; may be NULL */, int what, const cg_rules* rules,
+                             int mode);
+/* *kind = CG_PROFILE_STARTS, CG_PROFILE_INFLIGHT, CG_PROFILE_ADMITTED or
+ * CG_PROFILE_DROPPED: what the readable profile holds.  CG_EINVAL when no
+ * profile is readable. */
 int cg_profile_kind(cg_ctx* ctx, int* kind);
 /* Per node row [first_node, first_node + count) of the last profile's node
  * matrix (of either kind): its largest cell and the first bucket attaining it;

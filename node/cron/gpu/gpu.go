@@ -487,6 +487,8 @@ func (e *Engine) ProfilePerNode(sp *Specs, z *Zone, t0 time.Time, width time.Dur
 const (
 	ProfileStarts   = C.CG_PROFILE_STARTS
 	ProfileInFlight = C.CG_PROFILE_INFLIGHT
+	ProfileAdmitted = C.CG_PROFILE_ADMITTED
+	ProfileDropped  = C.CG_PROFILE_DROPPED
 )
 
 // durations checks one duration per rule and returns the pointer C reads
@@ -507,8 +509,8 @@ func durations(durMs []int64, nRules int) (*C.int64_t, error) {
 // over (t0, t0 + nBuckets*width] with edge - d < t <= edge, d = durMs[r]/1000
 // rounded up (not lockTtl's cost, which rounds down); totals[b] are the column
 // sums.  Commands started at or before t0 are not counted, so a row ramps up
-// over its first d seconds; Parallels drops and the KindAlone / KindInterval
-// locks are not modelled.  Like the rest of this file it has not been
+// over its first d seconds; every fire is counted (the fires Job.limit drops
+// are Admit's) and the KindAlone / KindInterval locks are not modelled.  Like the rest of this file it has not been
 // compiled here; tests/native/abi_inflight_c.c runs the same calls from C.
 func (e *Engine) InFlight(sp *Specs, z *Zone, t0 time.Time, width time.Duration, nBuckets int, durMs []int64) (inFlight []int32, totals []int64, err error) {
 	defer runtime.KeepAlive(e)
@@ -570,8 +572,108 @@ func (e *Engine) InFlightPerNode(sp *Specs, z *Zone, t0 time.Time, width time.Du
 	return nodes, totals, nil
 }
 
-// ProfileKind reports what the readable profile holds: ProfileStarts or
-// ProfileInFlight.
+// admitArgs checks one limit and (unless unit is nil) one unit per rule and
+// returns the pointers C reads.
+func admitArgs(parallels []int64, unit []int32, nRules int) (*C.int64_t, *C.int32_t, error) {
+	if len(parallels) != nRules {
+		return nil, nil, fmt.Errorf("gpu: %d parallels for %d rules", len(parallels), nRules)
+	}
+	if unit != nil && len(unit) != nRules {
+		return nil, nil, fmt.Errorf("gpu: %d units for %d rules", len(unit), nRules)
+	}
+	if nRules == 0 {
+		return nil, nil, nil
+	}
+	var u *C.int32_t
+	if unit != nil {
+		u = (*C.int32_t)(unsafe.Pointer(&unit[0]))
+	}
+	return (*C.int64_t)(unsafe.Pointer(&parallels[0])), u, nil
+}
+
+// Admit counts, per rule and bucket, the fires Job.limit (job.go:165-187)
+// would let run (what = ProfileAdmitted) or drop (ProfileDropped): a unit's
+// fires -- the rules with equal unit[r], non-decreasing along r; nil: every
+// rule alone -- are taken in (time, rule) order, and one is admitted while
+// fewer than parallels[r] admitted fires a of the unit have a + d > t, d =
+// durMs[r]/1000 rounded up; parallels 0 is unlimited.  Commands started at or
+// before t0 are unknown, fires of one second are taken in rule order, and the
+// KindAlone / KindInterval locks across nodes are not modelled.  Not compiled
+// here; tests/native/abi_admit_c.c runs the same calls from C.
+func (e *Engine) Admit(sp *Specs, z *Zone, t0 time.Time, width time.Duration, nBuckets int, durMs, parallels []int64, unit []int32, what int) (counts []int32, totals []int64, err error) {
+	defer runtime.KeepAlive(e)
+	defer runtime.KeepAlive(sp)
+	defer runtime.KeepAlive(z)
+	defer runtime.KeepAlive(durMs)
+	defer runtime.KeepAlive(parallels)
+	defer runtime.KeepAlive(unit)
+	d, err := durations(durMs, sp.n)
+	if err != nil {
+		return nil, nil, err
+	}
+	p, u, err := admitArgs(parallels, unit, sp.n)
+	if err != nil {
+		return nil, nil, err
+	}
+	if rc := C.cg_admit_device(e.ctx, sp.s, z.z, C.int64_t(t0.Unix()), C.int64_t(width/time.Second),
+		C.int32_t(nBuckets), d, p, u, C.int(what)); rc != 0 {
+		return nil, nil, lastErr(rc)
+	}
+	return e.profileRules(sp.n, nBuckets)
+}
+
+// AdmitPerNode is Admit summed per node: node ID -> admitted or dropped fires
+// per bucket over the rules that node runs (ProfilePerNode's join); exact when
+// the rules of a unit run on the same nodes.  totals are Admit's.
+func (e *Engine) AdmitPerNode(sp *Specs, z *Zone, t0 time.Time, width time.Duration, nBuckets int, durMs, parallels []int64, unit []int32, what int, j *Jobset, mode int) (nodes map[string][]int64, totals []int64, err error) {
+	defer runtime.KeepAlive(e)
+	defer runtime.KeepAlive(sp)
+	defer runtime.KeepAlive(z)
+	defer runtime.KeepAlive(j)
+	defer runtime.KeepAlive(durMs)
+	defer runtime.KeepAlive(parallels)
+	defer runtime.KeepAlive(unit)
+	d, err := durations(durMs, sp.n)
+	if err != nil {
+		return nil, nil, err
+	}
+	p, u, err := admitArgs(parallels, unit, sp.n)
+	if err != nil {
+		return nil, nil, err
+	}
+	var rin C.cg_rules_in
+	if rc := C.cg_jobset_rules(j.js, &rin); rc != 0 {
+		return nil, nil, lastErr(rc)
+	}
+	var r *C.cg_rules
+	if rc := C.cg_rules_upload(e.ctx, &rin, &r); rc != 0 {
+		return nil, nil, lastErr(rc)
+	}
+	defer C.cg_rules_free(r) // the node matrix stays in the engine's own buffers
+	if rc := C.cg_admit_per_node_device(e.ctx, sp.s, z.z, C.int64_t(t0.Unix()), C.int64_t(width/time.Second),
+		C.int32_t(nBuckets), d, p, u, C.int(what), r, C.int(mode)); rc != 0 {
+		return nil, nil, lastErr(rc)
+	}
+	nn := int(rin.n_nodes)
+	cnt := make([]int64, nn*nBuckets)
+	if len(cnt) > 0 {
+		if rc := C.cg_profile_copy_nodes(e.ctx, 0, C.int32_t(nn), (*C.int64_t)(unsafe.Pointer(&cnt[0]))); rc != 0 {
+			return nil, nil, lastErr(rc)
+		}
+	}
+	totals = make([]int64, nBuckets)
+	if rc := C.cg_profile_copy_totals(e.ctx, (*C.int64_t)(unsafe.Pointer(&totals[0]))); rc != 0 {
+		return nil, nil, lastErr(rc)
+	}
+	nodes = make(map[string][]int64, nn)
+	for n := 0; n < nn; n++ {
+		nodes[C.GoString(C.cg_jobset_node_id(j.js, C.int32_t(n)))] = cnt[n*nBuckets : (n+1)*nBuckets]
+	}
+	return nodes, totals, nil
+}
+
+// ProfileKind reports what the readable profile holds: ProfileStarts,
+// ProfileInFlight, ProfileAdmitted or ProfileDropped.
 func (e *Engine) ProfileKind() (int, error) {
 	defer runtime.KeepAlive(e)
 	var kind C.int
