@@ -34,6 +34,8 @@ EXCLUDE_NONE, EXCLUDE_RULE, EXCLUDE_CUMULATIVE = 0, 1, 2
 NODE_ORDER_RULE, NODE_ORDER_TIME = 0, 1  # cg_set_node_order
 PROFILE_STARTS, PROFILE_INFLIGHT = 0, 1  # CG_PROFILE_*: cg_profile_kind
 PROFILE_ADMITTED, PROFILE_DROPPED = 2, 3  # the two kinds of cg_admit_*
+PROFILE_LOCK_GRANTED, PROFILE_LOCK_SKIPPED = 4, 5  # the two kinds of cg_lock_profile_*
+JOB_COMMON, JOB_ALONE, JOB_INTERVAL = 0, 1, 2  # CG_JOB_*: Job.Kind (job.go:30-34)
 ADMIT_MAX_PARALLELS = 16  # CG_ADMIT_MAX_PARALLELS: the largest limit of a unit that can drop
 CG_FANOUT_AUTO, CG_FANOUT_FILTER, CG_FANOUT_DUE = 0, 1, 2  # cg_dispatcher_set_fanout_path
 UPCOMING_MAX = 65536  # CG_UPCOMING_MAX: the largest k of cg_dispatcher_upcoming*
@@ -202,6 +204,9 @@ def _declare(L):
         "cg_inflight_per_node_device": ([vp, vp, vp, i64, i64, i32, vp, vp, C.c_int], C.c_int),
         "cg_admit_device": ([vp, vp, vp, i64, i64, i32, vp, vp, vp, C.c_int], C.c_int),
         "cg_admit_per_node_device": ([vp, vp, vp, i64, i64, i32, vp, vp, vp, C.c_int, vp, C.c_int], C.c_int),
+        "cg_lock_profile_device": ([vp, vp, vp, i64, i64, i32, vp, vp, vp, vp, i64, C.c_int], C.c_int),
+        "cg_lock_profile_per_node_device": ([vp, vp, vp, i64, i64, i32, vp, vp, vp, vp, i64, C.c_int, vp, C.c_int],
+                                            C.c_int),
         "cg_profile_kind": ([vp, P(C.c_int)], C.c_int),
         "cg_profile_node_peaks": ([vp, i32, i32, vp, vp], C.c_int),
         "cg_profile_top_rules_nodes": ([vp, i32, vp], C.c_int),

@@ -121,6 +121,9 @@ struct RunSet {
   bool plan_valid = false;
   uint64_t plan_zone = 0;
   int64_t plan_t0 = 0, plan_t1 = 0;
+  // the plan's zone table reaches as far as cg_lock_ttl_batch's (a lock
+  // profile's; lock_table of run_set_count_scan): part of the cache key
+  bool plan_lock_table = false;
   // The stuck word holds ~0 whenever a count starts: k_count only lowers it
   // (atomicMin of a stuck rule) and the scan behind it copies it into the
   // record and stores ~0 again.  run_set_count_scan sets it once, before the
@@ -247,8 +250,9 @@ struct cg_ctx {
   // k_profile_walk, k_profile_totals, join + transpose when rebuilt, the
   // node matrix; of an in-flight call k_inflight_rules and k_inflight_walk
   // in the first two), [19..20] the last admission profile's own kernels
-  // (k_admit_prepare, k_admit_units; 0 after any other profile call)
-  float kt[21] = {0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0};
+  // (k_admit_prepare, k_admit_units; 0 after any other profile call), [21]
+  // the last lock profile's unit walk (k_lock_units; its k_admit_prepare in [19])
+  float kt[22] = {0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0};
   // expansion phase timing: 2 = an event between every phase (kt[0..5]);
   // 1 = events around k_write_cf only (kt[3]; the others read -1).  Each
   // event recorded between two kernels costs 6-12 us of idle GPU on this
@@ -375,10 +379,14 @@ struct cg_ctx {
   DBuf<int32_t> pf_peak_bucket;
   bool pf_peaks_valid = false;
   // an admission call's compacted units that can drop (cg::AdmitUnit, 24 B
-  // each) and its per-rule "unit can drop" flags [R], uploaded per call
+  // each) and its per-rule "unit can drop" flags [R], uploaded per call; of a
+  // lock profile the compacted lock units (cg::LockUnit, 32 B each) and the
+  // "contending rule of a lock unit" flags
   DBuf<char> pf_admit_units;
   DBuf<uint8_t> pf_admit_flag;
-  hipEvent_t pfev[8] = {};  // created by the first profile call ([6], [7]: around k_admit_units)
+  // k_lock_units lowers it from ~0 to a rule whose Next never returns (set before every launch)
+  DBuf<unsigned long long> pf_lock_stuck;
+  hipEvent_t pfev[8] = {};  // created by the first profile call ([6], [7]: around k_admit_prepare; the unit walk ends at [2])
   // The node matrix is summed over nt_off / nt_rule, which are the per-node
   // path's cache and may be rebuilt under a readable profile: nt_gen counts
   // the rebuilds (transpose_locked, and the dispatcher bind that takes the
@@ -431,7 +439,7 @@ struct cg_ctx {
     pf_rules.release(); pf_chunk_cnt.release(); pf_totals.release(); pf_nodes.release();
     pf_part.release(); pf_chunk_off.release();
     pf_dur.release(); pf_peak.release(); pf_peak_bucket.release();
-    pf_admit_units.release(); pf_admit_flag.release();
+    pf_admit_units.release(); pf_admit_flag.release(); pf_lock_stuck.release();
     for (hipEvent_t& e : pfev)
       if (e) (void)hipEventDestroy(e), e = nullptr;
   }
@@ -472,17 +480,19 @@ int plan_args(const cg::Plan& plan, const PlanLayout& L, char* dev_base, int64_t
 // rule}.  map_cap > 0: the scan also builds k_write_cf's slice map for an
 // output capacity of map_cap events (no k_chunk_map launch).  ev (or null):
 // three events recorded before the count, between the two and after the scan.
+// lock_table: the staged zone table reaches from the zero time to 12 years past
+// t1 (a lock profile's Next calls); segments, windows and flags are unchanged.
 // *empty: no rule or no segment -- nothing is counted, the record reads {0,
 // none} and rs.offsets [R+1] is left for the caller to zero.  The caller has
 // made sure that nothing enqueued earlier still reads or writes rs.
 int run_set_count_scan(RunSet& rs, const cg_specs* s, const cg_zone* z, int64_t t0, int64_t t1, int64_t map_cap,
-                       hipStream_t st, hipEvent_t* ev, bool* empty);
+                       hipStream_t st, hipEvent_t* ev, bool* empty, bool lock_table = false);
 // What a synchronous call does before its count and scan on the ctx stream
 // into c->rs (cg_expand.cpp): drains and discards pending pipelined calls,
 // clears the readable rule-major result, checks the horizon; an empty call's
 // offsets are zeroed and the stream drained.  c->mu held.
 int sync_count_scan(cg_ctx* c, const cg_specs* s, const cg_zone* z, int64_t t0, int64_t t1, bool* empty,
-                    int64_t map_cap = 0);
+                    int64_t map_cap = 0, bool lock_table = false);
 // the writers of the runs counted last into out (cap events: the capacity the
 // slice map was built for), on st: k_write_cf on `blocks` blocks, after_cf (or
 // null) recorded behind it, then k_write_walk when the plan has walked runs

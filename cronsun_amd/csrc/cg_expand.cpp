@@ -19,17 +19,20 @@ using namespace cg;
 
 // ------------------------------------------------------------ run-set chain
 int run_set_count_scan(RunSet& rs, const cg_specs* s, const cg_zone* z, int64_t t0, int64_t t1, int64_t map_cap,
-                       hipStream_t st, hipEvent_t* ev, bool* empty) {
+                       hipStream_t st, hipEvent_t* ev, bool* empty, bool lock_table) {
   int rc;
   const int64_t R = int64_t(s->n);
   if ((rc = rs.ensure_res())) return rc;
   // plan (cached across identical calls): packed into the pinned buffer here,
   // copied once every allocation below has succeeded
-  const bool fresh = !(rs.plan_valid && rs.plan_zone == z->serial && rs.plan_t0 == t0 && rs.plan_t1 == t1);
+  const bool fresh = !(rs.plan_valid && rs.plan_zone == z->serial && rs.plan_t0 == t0 && rs.plan_t1 == t1 &&
+                       rs.plan_lock_table == lock_table);
   PlanLayout L{};
   if (fresh) {
     rs.plan_valid = false;
     rs.plan = build_plan(z->rules, t0, t1);
+    // a lock profile's Next calls read past the horizon's table (cg_zone.h)
+    if (lock_table) rs.plan.table = build_lock_table(z->rules, t0, t1);
     L = plan_layout(rs.plan);
     if (rs.plan_pin_cap < L.bytes) {
       if (rs.plan_pin) (void)hipHostFree(rs.plan_pin);
@@ -57,6 +60,7 @@ int run_set_count_scan(RunSet& rs, const cg_specs* s, const cg_zone* z, int64_t 
     rs.plan_zone = z->serial;
     rs.plan_t0 = t0;
     rs.plan_t1 = t1;
+    rs.plan_lock_table = lock_table;
   }
   rs.R = R;
   rs.cap = map_cap;
@@ -96,7 +100,7 @@ std::string stuck_msg(unsigned long long rule) {
 // What a synchronous call does before its count and scan on the ctx stream
 // into c->rs; an empty call's offsets are zeroed and the stream drained.
 int sync_count_scan(cg_ctx* c, const cg_specs* s, const cg_zone* z, int64_t t0, int64_t t1, bool* empty,
-                    int64_t map_cap) {
+                    int64_t map_cap, bool lock_table) {
   // no readable result until this call succeeds (the accessors check last_R/E).
   // Asynchronous calls still pending are drained and their results and errors
   // discarded: this call's result replaces them (cronsun_gpu.h).
@@ -117,7 +121,8 @@ int sync_count_scan(cg_ctx* c, const cg_specs* s, const cg_zone* z, int64_t t0, 
   if (t1 - t0 > CG_MAX_HORIZON || t0 < -(int64_t(1) << 45) || t1 > (int64_t(1) << 45))
     return cg_fail(CG_ERANGE, "horizon must satisfy t1 - t0 <= CG_MAX_HORIZON (40 years)");
   for (int i = 0; i < 6; i++) c->kt[i] = 0;
-  int rc = run_set_count_scan(c->rs, s, z, t0, t1, map_cap, c->st, c->phase_timing >= 2 ? c->ev : nullptr, empty);
+  int rc = run_set_count_scan(c->rs, s, z, t0, t1, map_cap, c->st, c->phase_timing >= 2 ? c->ev : nullptr, empty,
+                              lock_table);
   if (rc) return rc;
   if (*empty) {
     HIPCHK(hipMemsetAsync(c->rs.offsets.p, 0, (int64_t(s->n) + 1) * 8, c->st));

@@ -31,6 +31,15 @@
 //                     admitted fires (cg_admit.h, admit_walk_unit) and adds
 //                     (ADMITTED) or subtracts (DROPPED) 1 in the rule's own row
 // and totals, node matrix and accessors are shared.
+//
+// Lock profile (cg_lock_profile_*): the fires the KindAlone / KindInterval
+// lock of Cmd.Run would grant, or those it would skip.  The admission chain
+// with the unit walk replaced:
+//   k_admit_prepare   flag = contending rule of a lock unit (GRANTED: those
+//                     rows restart from zero; SKIPPED: all other rows are zero)
+//   k_lock_units      one lane per lock unit with a contending rule: walks the
+//                     unit's granted fires (cg_lock.h, lock_walk_unit) and adds
+//                     (GRANTED) or subtracts (SKIPPED) 1 in the rule's own row
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
@@ -40,6 +49,7 @@
 #include "../../include/cronsun_gpu.h"
 #include "cg_api_internal.h"
 #include "cg_admit.h"
+#include "cg_lock.h"
 #include "cg_profile.h"
 #include "cg_stage.h"
 
@@ -53,6 +63,9 @@ constexpr int kMaxBuckets = 4096;
 constexpr int kTotalChunk = 4096;
 static_assert(kAdmitMaxParallels == CG_ADMIT_MAX_PARALLELS, "cg_admit.h and the public header disagree");
 static_assert(sizeof(AdmitUnit) == 24, "AdmitUnit is uploaded as 24-byte records");
+static_assert(sizeof(LockUnit) == 32, "LockUnit is uploaded as 32-byte records");
+static_assert(JOB_COMMON == CG_JOB_COMMON && JOB_ALONE == CG_JOB_ALONE && JOB_INTERVAL == CG_JOB_INTERVAL,
+              "cg_time.h and the public header disagree");
 
 // ------------------------------------------------------------ rule matrix --
 __global__ __launch_bounds__(256) void k_profile_rules(const DSpec* __restrict__ specs, int64_t R, PlanArgs p,
@@ -219,6 +232,44 @@ __global__ __launch_bounds__(kAdmitBlock) void k_admit_units(const DSpec* __rest
                     const int64_t b = (t - t0 - 1) / w;
                     if (t > t0 && b < B) out[r * B + b] += step;
                   });
+}
+
+// ----------------------------------------------------------- lock profile --
+// One lane per lock unit with a contending rule (units [U], compacted by the
+// host so waves are dense); a block is one wave.  The lane walks the unit's
+// granted fires and adds `step` (+1 GRANTED, -1 SKIPPED: start - granted) to
+// the cell of the firing rule's row -- a row belongs to one unit, so plain
+// read-modify-write.  contends [R]: the prepare pass's flags, inside a lock
+// unit "this rule reaches the lock".  The walked runs' remembered positions
+// (cg_admit.h) live in LDS behind the staged plan, [slot][lane]; there is no
+// ring.  A rule whose Next never returns lowers *stuck to its index.
+constexpr int kLockBlock = 64;
+__global__ __launch_bounds__(kLockBlock) void k_lock_units(const DSpec* __restrict__ specs, PlanArgs p,
+                                                            const int64_t* __restrict__ run_anchor,
+                                                            const int32_t* __restrict__ run_count,
+                                                            const uint32_t* __restrict__ run_dmask,
+                                                            const LockUnit* __restrict__ units, int64_t U,
+                                                            const uint8_t* __restrict__ contends, size_t cache_off,
+                                                            int64_t lock_ttl, int64_t w, int32_t B, int32_t step,
+                                                            int32_t* __restrict__ out,
+                                                            unsigned long long* __restrict__ stuck) {
+  extern __shared__ __align__(16) char lds[];
+  PlanView v = stage_plan(p, lds);
+  // [walk t 8] i64, then [rel 8][s 8][q 8] i32, each [slot][lane]
+  int64_t* wt = reinterpret_cast<int64_t*>(lds + cache_off) + threadIdx.x;
+  int32_t* w32 = reinterpret_cast<int32_t*>(lds + cache_off + size_t(kAdmitWalkSlots) * kLockBlock * 8) + threadIdx.x;
+  const AdmitWalkCache wc{wt, w32, w32 + kAdmitWalkSlots * kLockBlock, w32 + 2 * kAdmitWalkSlots * kLockBlock,
+                          kLockBlock};
+  const int64_t i = blockIdx.x * int64_t(kLockBlock) + threadIdx.x;
+  if (i >= U) return;
+  const LockUnit u = units[i];
+  const int64_t t0 = p.t0;
+  const int64_t bad = lock_walk_unit(specs, v.z, v.segs, p.G, run_anchor, run_count, run_dmask, t0, p.t1, u, lock_ttl,
+                                     contends, wc, [&](int64_t r, int64_t t) {
+                                       const int64_t b = (t - t0 - 1) / w;
+                                       if (t > t0 && b < B) out[r * B + b] += step;
+                                     });
+  if (bad >= 0) atomicMin(stuck, static_cast<unsigned long long>(bad));
 }
 
 // one wave per row of the node matrix: (largest cell, first bucket attaining
@@ -398,23 +449,32 @@ struct AdmitCall {
   std::vector<AdmitUnit> units;
   std::vector<uint8_t> flag;
 };
+// A lock call's: the lock units with a contending rule, compacted, and per
+// rule whether it is a contending rule of a lock unit.
+struct LockCall {
+  int what = CG_PROFILE_LOCK_SKIPPED;
+  int64_t lock_ttl = 0;
+  std::vector<LockUnit> units;
+  std::vector<uint8_t> flag;
+};
 
 int profile_rules_enqueue(cg_ctx* c, const cg_specs* s, const cg_zone* z, int64_t t0, int64_t w, int32_t B,
-                          const std::vector<int64_t>* dsec, const AdmitCall* adm = nullptr) {
+                          const std::vector<int64_t>* dsec, const AdmitCall* adm = nullptr,
+                          const LockCall* lk = nullptr) {
   c->pf_valid = false;
   c->pf_has_nodes = false;
   c->pf_peaks_valid = false;
   c->tr_valid = false;  // a top-rules result does not outlive its profile
   int rc;
   bool empty = true;
-  if ((rc = sync_count_scan(c, s, z, t0, t0 + int64_t(B) * w, &empty))) return rc;
+  if ((rc = sync_count_scan(c, s, z, t0, t0 + int64_t(B) * w, &empty, 0, lk != nullptr))) return rc;
   if ((rc = ensure_events(c))) return rc;
   const int64_t R = int64_t(s->n);
   if ((rc = c->pf_rules.ensure(size_t(std::max<int64_t>(R * B, 1)))) || (rc = c->pf_totals.ensure(size_t(B))))
     return rc;
   hipStream_t st = c->st;
   HIPCHK(hipMemsetAsync(c->pf_totals.p, 0, size_t(B) * 8, st));
-  for (int i = 14; i < 21; i++) c->kt[i] = 0.f;
+  for (int i = 14; i < 22; i++) c->kt[i] = 0.f;
   for (int i : {0, 1, 6, 7, 2, 3}) (void)hipEventRecord(c->pfev[i], st);
   if (!empty) {
     RunSet& rs = c->rs;
@@ -423,6 +483,9 @@ int profile_rules_enqueue(cg_ctx* c, const cg_specs* s, const cg_zone* z, int64_
     const unsigned long long stuck = static_cast<unsigned long long>(rs.res_host[1]);
     if (stuck != ~0ULL) return cg_fail(CG_ERANGE, stuck_msg(stuck));
     const size_t lds = plan_lds_bytes(rs.pa);
+    const size_t cache_off = align_up(lds, 16), lock_lds = cache_off + size_t(kLockBlock) * kLockLaneBytes;
+    if (lk && !lk->units.empty() && lock_lds > 64 * 1024)
+      return cg_fail(CG_ERANGE, "cg_lock_profile: the plan of this horizon leaves no LDS for the walked runs' positions");
     if (dsec) {
       // (*dsec outlives the stream synchronise that ends the call)
       if ((rc = c->pf_dur.ensure(size_t(R)))) return rc;
@@ -464,7 +527,40 @@ int profile_rules_enqueue(cg_ctx* c, const cg_specs* s, const cg_zone* z, int64_
                            reinterpret_cast<const AdmitUnit*>(c->pf_admit_units.p), U, ring_off, w, B,
                            adm->what == CG_PROFILE_ADMITTED ? 1 : -1, c->pf_rules.p);
     }
-    (void)hipEventRecord(c->pfev[2], st);
+    if (lk) {
+      const int64_t U = int64_t(lk->units.size());
+      if ((rc = c->pf_admit_flag.ensure(size_t(R))) ||
+          (rc = c->pf_admit_units.ensure(size_t(std::max<int64_t>(U, 1)) * sizeof(LockUnit))) ||
+          (rc = c->pf_lock_stuck.ensure(1)))
+        return rc;
+      HIPCHK(hipMemcpyAsync(c->pf_admit_flag.p, lk->flag.data(), size_t(R), hipMemcpyHostToDevice, st));
+      if (U > 0)
+        HIPCHK(hipMemcpyAsync(c->pf_admit_units.p, lk->units.data(), size_t(U) * sizeof(LockUnit), hipMemcpyHostToDevice, st));
+      HIPCHK(hipMemsetAsync(c->pf_lock_stuck.p, 0xFF, sizeof(unsigned long long), st));
+      (void)hipEventRecord(c->pfev[6], st);
+      hipLaunchKernelGGL(k_admit_prepare, dim3(gridn(R * B, 256, 4096)), dim3(256), 0, st, c->pf_admit_flag.p, R, B,
+                         lk->what == CG_PROFILE_LOCK_GRANTED ? 1 : 0, c->pf_rules.p);
+      (void)hipEventRecord(c->pfev[7], st);
+      if (U > 0)
+        hipLaunchKernelGGL(k_lock_units, dim3(unsigned((U + kLockBlock - 1) / kLockBlock)), dim3(kLockBlock), lock_lds, st,
+                           s->d, rs.pa, rs.run_anchor.p, rs.run_count.p, rs.run_dmask.p,
+                           reinterpret_cast<const LockUnit*>(c->pf_admit_units.p), U, c->pf_admit_flag.p, cache_off,
+                           lk->lock_ttl, w, B, lk->what == CG_PROFILE_LOCK_GRANTED ? 1 : -1, c->pf_rules.p,
+                           c->pf_lock_stuck.p);
+      (void)hipEventRecord(c->pfev[2], st);
+      HIPCHK(hipGetLastError());
+      // a granted fire whose Next never returns: the reference hangs in
+      // lockTtl there, and the unit's rows are unfinished -- no profile
+      unsigned long long lstuck = ~0ULL;
+      HIPCHK(hipMemcpyAsync(&lstuck, c->pf_lock_stuck.p, sizeof lstuck, hipMemcpyDeviceToHost, st));
+      HIPCHK(hipStreamSynchronize(st));
+      if (lstuck != ~0ULL)
+        return cg_fail(CG_ERANGE, "cg_lock_profile: rule " + std::to_string(lstuck) +
+                                      ": Next never returns from a fire of this horizon that finds the lock free "
+                                      "(the reference's lockTtl does not return there)");
+    } else {
+      (void)hipEventRecord(c->pfev[2], st);
+    }
     hipLaunchKernelGGL(k_profile_totals, dim3(gridn(R, kTotalChunk, 1 << 30), (B + 63) / 64), dim3(256), 0, st,
                        c->pf_rules.p, R, B, reinterpret_cast<unsigned long long*>(c->pf_totals.p));
     (void)hipEventRecord(c->pfev[3], st);
@@ -473,7 +569,7 @@ int profile_rules_enqueue(cg_ctx* c, const cg_specs* s, const cg_zone* z, int64_
   c->pf_R = R;
   c->pf_B = B;
   c->pf_N = 0;
-  c->pf_kind = adm ? adm->what : dsec ? CG_PROFILE_INFLIGHT : CG_PROFILE_STARTS;
+  c->pf_kind = lk ? lk->what : adm ? adm->what : dsec ? CG_PROFILE_INFLIGHT : CG_PROFILE_STARTS;
   return CG_OK;
 }
 
@@ -484,6 +580,11 @@ void profile_rule_times(cg_ctx* c) {
     (void)hipEventElapsedTime(&c->kt[15], c->pfev[1], c->pfev[6]);
     (void)hipEventElapsedTime(&c->kt[19], c->pfev[6], c->pfev[7]);
     (void)hipEventElapsedTime(&c->kt[20], c->pfev[7], c->pfev[2]);
+  }
+  if (c->pf_kind == CG_PROFILE_LOCK_GRANTED || c->pf_kind == CG_PROFILE_LOCK_SKIPPED) {
+    (void)hipEventElapsedTime(&c->kt[15], c->pfev[1], c->pfev[6]);
+    (void)hipEventElapsedTime(&c->kt[19], c->pfev[6], c->pfev[7]);
+    (void)hipEventElapsedTime(&c->kt[21], c->pfev[7], c->pfev[2]);
   }
   // the count and scan behind it, when the chain recorded their events ([0], [1])
   if (c->phase_timing >= 2 && c->pf_R > 0) {
@@ -511,10 +612,10 @@ int inflight_durations(const char* what, const cg_specs* s, const int64_t* dur_m
 
 // the rule-matrix call of either kind (dsec null: starts); arguments checked
 int profile_call(cg_ctx* c, const cg_specs* s, const cg_zone* z, int64_t t0, int64_t width, int32_t n_buckets,
-                 const std::vector<int64_t>* dsec, const AdmitCall* adm = nullptr) {
+                 const std::vector<int64_t>* dsec, const AdmitCall* adm = nullptr, const LockCall* lk = nullptr) {
   std::lock_guard<std::mutex> g(c->mu);
   (void)hipGetLastError();  // clear a stale error so launch checks see only their own
-  int rc = profile_rules_enqueue(c, s, z, t0, width, n_buckets, dsec, adm);
+  int rc = profile_rules_enqueue(c, s, z, t0, width, n_buckets, dsec, adm, lk);
   if (rc) return rc;
   HIPCHK(hipStreamSynchronize(c->st));
   profile_rule_times(c);
@@ -563,6 +664,50 @@ int admit_units(const char* what_fn, const cg_specs* s, const int64_t* dur_ms, c
   return CG_OK;
 }
 
+// A lock call's per-rule arguments -> the lock units with a contending rule.
+// Units are the maximal runs of equal unit[] (NULL: every rule its own); all
+// checks name the first offending rule.
+int lock_units(const char* what_fn, const cg_specs* s, const int32_t* kind, const int64_t* avg_ms, const int32_t* unit,
+               const uint8_t* contends, int64_t lock_ttl, int what, int64_t horizon, LockCall* out) {
+  const std::string fn(what_fn);
+  if (what != CG_PROFILE_LOCK_GRANTED && what != CG_PROFILE_LOCK_SKIPPED)
+    return cg_fail(CG_EINVAL, fn + ": what must be CG_PROFILE_LOCK_GRANTED or CG_PROFILE_LOCK_SKIPPED");
+  if (lock_ttl < 2) return cg_fail(CG_EINVAL, fn + ": lock_ttl must be at least 2 (conf.go:136-138)");
+  const int64_t R = int64_t(s->n);
+  if (R > 0 && !kind) return cg_fail(CG_EINVAL, fn + ": rule 0: null kind");
+  if (R > 0 && !avg_ms) return cg_fail(CG_EINVAL, fn + ": rule 0: null avg_time_ms");
+  for (int64_t r = 0; r < R; r++) {
+    if (kind[r] != CG_JOB_COMMON && kind[r] != CG_JOB_ALONE && kind[r] != CG_JOB_INTERVAL)
+      return cg_fail(CG_EINVAL, fn + ": rule " + std::to_string(r) + ": kind " + std::to_string(kind[r]) +
+                                    " is not CG_JOB_COMMON, CG_JOB_ALONE or CG_JOB_INTERVAL");
+    if (unit && r > 0 && unit[r] < unit[r - 1])
+      return cg_fail(CG_EINVAL, fn + ": rule " + std::to_string(r) + ": unit decreases");
+  }
+  out->what = what;
+  out->lock_ttl = lock_ttl;
+  out->units.clear();
+  out->flag.assign(size_t(R), 0);
+  for (int64_t r0 = 0; r0 < R;) {
+    int64_t r1 = r0 + 1;
+    if (unit)
+      for (; r1 < R && unit[r1] == unit[r0]; r1++)
+        if (kind[r1] != kind[r0] || avg_ms[r1] != avg_ms[r0])
+          return cg_fail(CG_EINVAL, fn + ": rule " + std::to_string(r1) + ": kind / avg_time_ms differ inside unit " +
+                                        std::to_string(unit[r0]));
+    if (kind[r0] != CG_JOB_COMMON) {
+      if (r1 - r0 > INT32_MAX) return cg_fail(CG_ERANGE, fn + ": rule " + std::to_string(r0) + ": unit too long");
+      bool any = false;
+      for (int64_t r = r0; r < r1; r++)
+        if (!contends || contends[r]) any = true, out->flag[size_t(r)] = 1;
+      if (any)
+        out->units.push_back(LockUnit{r0, avg_ms[r0], inflight_seconds(std::max<int64_t>(avg_ms[r0], 0), horizon),
+                                      int32_t(r1 - r0), kind[r0]});
+    }
+    r0 = r1;
+  }
+  return CG_OK;
+}
+
 int profile_check_node_args(const char* what, const cg_specs* s, const cg_rules* rules, int mode) {
   if (!rules) return cg_fail(CG_EINVAL, std::string(what) + ": null");
   if (mode < 0 || mode > 2) return cg_fail(CG_EINVAL, "bad exclude mode");
@@ -573,12 +718,12 @@ int profile_check_node_args(const char* what, const cg_specs* s, const cg_rules*
 // the per-node call of either kind; arguments checked
 int profile_per_node_call(cg_ctx* c, const cg_specs* s, const cg_zone* z, int64_t t0, int64_t width,
                           int32_t n_buckets, const cg_rules* rules, int mode, const std::vector<int64_t>* dsec,
-                          const AdmitCall* adm = nullptr) {
+                          const AdmitCall* adm = nullptr, const LockCall* lk = nullptr) {
   const RulesStore& in = rules->st;
   std::lock_guard<std::mutex> g(c->mu);
   (void)hipGetLastError();
   const int32_t B = n_buckets, N = in.n_nodes;
-  int rc = profile_rules_enqueue(c, s, z, t0, width, B, dsec, adm);
+  int rc = profile_rules_enqueue(c, s, z, t0, width, B, dsec, adm, lk);
   if (rc) return rc;
   hipStream_t st = c->st;
   // the rule->node join and its transpose: the per-node path's cache, keyed
@@ -686,6 +831,30 @@ int cg_admit_per_node_device(cg_ctx* c, const cg_specs* s, const cg_zone* z, int
                            &adm))
     return rc;
   return profile_per_node_call(c, s, z, t0, width, n_buckets, rules, mode, nullptr, &adm);
+}
+
+int cg_lock_profile_device(cg_ctx* c, const cg_specs* s, const cg_zone* z, int64_t t0, int64_t width,
+                           int32_t n_buckets, const int32_t* kind, const int64_t* avg_time_ms, const int32_t* unit,
+                           const uint8_t* contends, int64_t lock_ttl, int what) {
+  LockCall lk;
+  if (int rc = profile_check_args("cg_lock_profile_device", c, s, z, width, n_buckets)) return rc;
+  if (int rc = lock_units("cg_lock_profile_device", s, kind, avg_time_ms, unit, contends, lock_ttl, what,
+                          int64_t(n_buckets) * width, &lk))
+    return rc;
+  return profile_call(c, s, z, t0, width, n_buckets, nullptr, nullptr, &lk);
+}
+
+int cg_lock_profile_per_node_device(cg_ctx* c, const cg_specs* s, const cg_zone* z, int64_t t0, int64_t width,
+                                    int32_t n_buckets, const int32_t* kind, const int64_t* avg_time_ms,
+                                    const int32_t* unit, const uint8_t* contends, int64_t lock_ttl, int what,
+                                    const cg_rules* rules, int mode) {
+  LockCall lk;
+  if (int rc = profile_check_args("cg_lock_profile_per_node_device", c, s, z, width, n_buckets)) return rc;
+  if (int rc = profile_check_node_args("cg_lock_profile_per_node_device", s, rules, mode)) return rc;
+  if (int rc = lock_units("cg_lock_profile_per_node_device", s, kind, avg_time_ms, unit, contends, lock_ttl, what,
+                          int64_t(n_buckets) * width, &lk))
+    return rc;
+  return profile_per_node_call(c, s, z, t0, width, n_buckets, rules, mode, nullptr, nullptr, &lk);
 }
 
 int cg_profile_kind(cg_ctx* c, int* kind) {

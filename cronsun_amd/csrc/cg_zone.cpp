@@ -371,6 +371,14 @@ ZoneTable build_table(const ZoneRules& z, int64_t lo, int64_t hi) {
   return t;
 }
 
+// The zone table of a lock profile's plan: its two Next calls per granted fire
+// read as far as a lockTtl batch's do -- ~12 years past a fire, and from the
+// zero time on when a rule never fires again.
+ZoneTable build_lock_table(const ZoneRules& z, int64_t t0, int64_t t1) {
+  const int64_t kDay = 86400;
+  return build_table(z, std::min<int64_t>(t0, CG_ZERO_TIME) - 64 * kDay, t1 + (12 * 366 + 64) * kDay);
+}
+
 // Is breakpoint i of table t a "clean" transition -- one the Go walk crosses
 // exactly as the closed form in the local time of each instant does, so it
 // needs no WALK window and no exact walk from T0 (clean

@@ -70,6 +70,11 @@ struct Plan {
   uint32_t flags = 0;  // kPlanT0Walk | kPlanFinalWalk | kPlanWalkSegs
 };
 Plan build_plan(const ZoneRules& z, int64_t t0, int64_t t1);
+// The table a lock profile stages in place of build_plan's (cg_lock.h): from
+// the zero time to 12 years past t1, as cg_lock_ttl_batch's.  Segments, WALK
+// windows and flags stay those built from the horizon's own table; the longer
+// one answers every lookup inside that one's range alike.
+ZoneTable build_lock_table(const ZoneRules& z, int64_t t0, int64_t t1);
 // breakpoint i (>= 1) of t is a clean transition: no WALK window, no exact
 // walk from T0 after it (cg_zone.cpp)
 bool clean_transition(const ZoneTable& t, size_t i);

@@ -22,6 +22,10 @@ seen from Python.  Wraps a cg_ctx (one HIP device + stream + HBM buffers).
                                             fires Job.limit() admits / drops per (rule, bucket)
   Engine.admit_per_node(specs, loc, t0, width, n_buckets, dur_ms, parallels, unit, drules, mode, what)
                                             ... per (node, bucket)
+  Engine.lock_runs(specs, loc, t0, width, n_buckets, kind, avg_time_ms, unit, contends, lock_ttl, what)
+                                            fires the KindAlone / KindInterval lock grants / skips
+  Engine.lock_runs_per_node(specs, loc, t0, width, n_buckets, kind, avg_time_ms, unit, contends, drules, mode, lock_ttl, what)
+                                            ... per (node, bucket)
   Engine.profile_node_peaks()               per node: largest cell, first bucket with it
   Engine.profile_top_rules(k, buckets=None) per node: the k rules with the largest
                                             cells of one bucket (default: its peak)
@@ -954,9 +958,113 @@ class Engine:
         check(lib().cg_last_kernel_times(self._h, buf, 21))
         return list(buf)[19:21]
 
+    # ------------------------------------------------------ lock profile
+    _LOCK_WHAT = {"granted": _lib.PROFILE_LOCK_GRANTED, "skipped": _lib.PROFILE_LOCK_SKIPPED}
+
+    def _lock_args(self, n, kind, avg_time_ms, unit, contends, lock_ttl, what):
+        """Checked host arrays of a lock call: (kind int32, avg_time_ms int64,
+        unit int32 or None, contends uint8 or None, lock_ttl, CG_PROFILE_*)."""
+        if what not in self._LOCK_WHAT:
+            raise ValueError(f"what must be 'granted' or 'skipped', got {what!r}")
+        k = np.ascontiguousarray(kind, dtype=np.int32)
+        if k.shape != (n,):
+            raise ValueError(f"kind must hold one Job.Kind per rule ({n}), got shape {k.shape}")
+        a = np.ascontiguousarray(avg_time_ms, dtype=np.int64)
+        if a.shape != (n,):
+            raise ValueError(f"avg_time_ms must hold one AvgTime per rule ({n}), got shape {a.shape}")
+        u = c = None
+        if unit is not None:
+            u = np.ascontiguousarray(unit, dtype=np.int32)
+            if u.shape != (n,):
+                raise ValueError(f"unit must hold one unit per rule ({n}), got shape {u.shape}")
+        if contends is not None:
+            c = np.ascontiguousarray(np.asarray(contends) != 0, dtype=np.uint8)
+            if c.shape != (n,):
+                raise ValueError(f"contends must hold one flag per rule ({n}), got shape {c.shape}")
+        if int(lock_ttl) < 2:
+            raise ValueError(f"lock_ttl must be at least 2 (conf.go:136-138), got {lock_ttl}")
+        return k, a, u, c, int(lock_ttl), self._LOCK_WHAT[what]
+
+    @staticmethod
+    def _ptr(a):
+        return None if a is None else a.ctypes.data
+
+    def lock_runs(self, specs, loc, t0, width, n_buckets, kind, avg_time_ms, unit=None, contends=None, lock_ttl=300,
+                  what="skipped"):
+        """Fires the KindAlone / KindInterval lock of Cmd.Run would grant
+        (what="granted") or skip (what="skipped") per rule and bucket
+        (cg_lock_profile_device): (rule matrix int32 [R, B], totals int64
+        [B]).  kind [R]: Job.Kind (_lib.JOB_*); avg_time_ms [R]: Job.AvgTime
+        as stored; unit [R] (non-decreasing, or None: every rule alone): the
+        job, cluster-wide -- its rules share one lock and must share kind and
+        avg_time_ms; contends [R] (or None: all): 0 where the rule reaches no
+        lock (rule_contends); lock_ttl: conf LockTtl.  A lock unit's
+        contending fires are taken in (time, rule) order: one is skipped while
+        t < free_at or when its lockTtl is 0, else granted with free_at = t +
+        ttl (INTERVAL) or t + ceil(AvgTime) + ttl (ALONE), ttl being
+        lock_ttl_batch at now = t.  granted + skipped == profile().  Locks
+        held at t0 are not known (cold start)."""
+        sp = self._specs(specs)
+        k, a, u, c, ttl, w = self._lock_args(sp.n, kind, avg_time_ms, unit, contends, lock_ttl, what)
+        check(lib().cg_lock_profile_device(self._h, sp._h, self._loc(loc).handle, int(t0), int(width), int(n_buckets),
+                                           k.ctypes.data, a.ctypes.data, self._ptr(u), self._ptr(c), ttl, w))
+        return self.profile_rules(), self.profile_totals()
+
+    def lock_runs_per_node(self, specs, loc, t0, width, n_buckets, kind, avg_time_ms, unit, contends, drules,
+                           mode=_lib.EXCLUDE_NONE, lock_ttl=300, what="skipped"):
+        """Granted or skipped fires per node and bucket
+        (cg_lock_profile_per_node_device): int64 [N, B], the lock rule matrix
+        summed over the rules each node runs under the exclude mode.  The
+        SKIPPED row is exact (the fires of the node's Cmds at which the job ran
+        on no node); the GRANTED row is an upper bound (the fires at which the
+        node contends for a free lock -- which node wins is etcd arrival
+        order).  Rule matrix, totals, peaks and top rules of the same call:
+        profile_rules() / profile_totals() / profile_node_peaks() /
+        profile_top_rules()."""
+        k, a, u, c, ttl, w = self._lock_args(specs.n, kind, avg_time_ms, unit, contends, lock_ttl, what)
+        check(lib().cg_lock_profile_per_node_device(self._h, specs._h, self._loc(loc).handle, int(t0), int(width),
+                                                    int(n_buckets), k.ctypes.data, a.ctypes.data, self._ptr(u),
+                                                    self._ptr(c), ttl, w, drules._h, int(mode)))
+        return self.profile_nodes()
+
+    def lock_runs_device(self, specs, loc, t0, width, n_buckets, kind, avg_time_ms, unit=None, contends=None,
+                         lock_ttl=300, what="skipped"):
+        """lock_runs() left in HBM: torch views (rule matrix, totals), valid
+        until the next profile call of any kind."""
+        k, a, u, c, ttl, w = self._lock_args(specs.n, kind, avg_time_ms, unit, contends, lock_ttl, what)
+        check(lib().cg_lock_profile_device(self._h, specs._h, self._loc(loc).handle, int(t0), int(width),
+                                           int(n_buckets), k.ctypes.data, a.ctypes.data, self._ptr(u), self._ptr(c),
+                                           ttl, w))
+        return self._profile_tensors()[:2]
+
+    def lock_runs_per_node_device(self, specs, loc, t0, width, n_buckets, kind, avg_time_ms, unit, contends, drules,
+                                  mode=_lib.EXCLUDE_NONE, lock_ttl=300, what="skipped"):
+        """lock_runs_per_node() left in HBM: torch views (rule matrix, totals,
+        node matrix)."""
+        k, a, u, c, ttl, w = self._lock_args(specs.n, kind, avg_time_ms, unit, contends, lock_ttl, what)
+        check(lib().cg_lock_profile_per_node_device(self._h, specs._h, self._loc(loc).handle, int(t0), int(width),
+                                                    int(n_buckets), k.ctypes.data, a.ctypes.data, self._ptr(u),
+                                                    self._ptr(c), ttl, w, drules._h, int(mode)))
+        return self._profile_tensors()
+
+    def rule_contends(self, rules, mode=_lib.EXCLUDE_NONE):
+        """uint8 [R] for a RulesIn: 1 where the rule is scheduled on some node
+        under the exclude mode (rule_nodes' degree > 0), 0 where it reaches no
+        lock: on no node, or replaced everywhere by a later rule with the same
+        Cmd key."""
+        return contends_of(self.rule_nodes(rules, mode)[0])
+
+    def lock_kernel_times(self):
+        """ms of the last lock call's own kernels (cg_last_kernel_times [19],
+        [21]): the pass that zeroes the rewritten rows, k_lock_units."""
+        buf = (C.c_float * 22)()
+        check(lib().cg_last_kernel_times(self._h, buf, 22))
+        return [buf[19], buf[21]]
+
     def profile_kind(self):
         """What the readable profile holds: _lib.PROFILE_STARTS,
-        PROFILE_INFLIGHT, PROFILE_ADMITTED or PROFILE_DROPPED (cg_profile_kind)."""
+        PROFILE_INFLIGHT, PROFILE_ADMITTED, PROFILE_DROPPED, PROFILE_LOCK_GRANTED
+        or PROFILE_LOCK_SKIPPED (cg_profile_kind)."""
         k = C.c_int()
         check(lib().cg_profile_kind(self._h, C.byref(k)))
         return k.value
@@ -1065,6 +1173,12 @@ class Engine:
 
 _default = None
 _default_lock = threading.Lock()
+
+
+def contends_of(rule_node_off):
+    """uint8 [R] from the offsets [R+1] of a rule->node join (Engine.rule_nodes):
+    1 where the rule runs on some node, 0 where it reaches no lock."""
+    return (np.diff(np.asarray(rule_node_off, dtype=np.int64)) > 0).astype(np.uint8)
 
 
 def default_engine():

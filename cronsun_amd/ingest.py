@@ -14,6 +14,10 @@ batch form of GetGroups("") + GetJobs() (group.go:39-63, job.go:339-365).
                                      commands running per node and bucket edge
   js.node_drops(t0, width, n_buckets)
                                      fires Job.limit() would drop per node and bucket
+  js.node_lock_skips(t0, width, n_buckets)
+                                     fires at which an exclusive job ran nowhere, per node and bucket
+  js.job_lock_runs(t0, width, n_buckets)
+                                     per exclusive job: runs and skipped fires per bucket
   js.node_peak_rules(t0, width, n_buckets, k)
                                      per node: peak, bucket, its top k rules there
 """
@@ -23,7 +27,8 @@ import numpy as np
 
 from . import _lib
 from ._lib import check, lib
-from .model import _Interned, admission_units, drops_of, durations_of, peak_rules_of
+from .model import (_Interned, admission_units, drops_of, durations_of, job_lock_runs_of, lock_skips_of,
+                    peak_rules_of)
 
 
 def _docs_array(docs):
@@ -110,6 +115,31 @@ class EtcdJobSet(_Interned):
         specs = eng.upload_c(self.schedules_c(), self.n_rules)
         return drops_of(self, eng, specs, rin, t0, width, n_buckets, dur, self.rule_parallels(), unit, loc, mode,
                         what), [self.job_id(j).decode() for j in split]
+
+    def rule_kinds(self):
+        """(kind int32 [n_rules], avg_time_ms int64 [n_rules]), as JobSet.rule_kinds."""
+        kind, avg, _ = self.job_meta()
+        rj = self.rules_in().rule_job[:self.n_rules]
+        return kind[rj].astype(np.int32), avg[rj].astype(np.int64)
+
+    def node_lock_skips(self, t0, width, n_buckets, loc=None, mode=_lib.EXCLUDE_NONE, lock_ttl=300, engine=None,
+                        what="skipped"):
+        """Fires per node and bucket at which a KindAlone / KindInterval job
+        ran on no node: {node ID: int64 [n_buckets]}, as JobSet.node_lock_skips."""
+        from .engine import default_engine
+        eng = engine or default_engine()
+        kind, avg = self.rule_kinds()
+        return lock_skips_of(self, eng, eng.upload_c(self.schedules_c(), self.n_rules), self.rules_in(), t0, width,
+                             n_buckets, kind, avg, loc, mode, lock_ttl, what)
+
+    def job_lock_runs(self, t0, width, n_buckets, loc=None, mode=_lib.EXCLUDE_NONE, lock_ttl=300, engine=None):
+        """{job ID: (granted [n_buckets], skipped [n_buckets])} for the
+        exclusive jobs, cluster-wide, as JobSet.job_lock_runs."""
+        from .engine import default_engine
+        eng = engine or default_engine()
+        kind, avg = self.rule_kinds()
+        return job_lock_runs_of(eng, eng.upload_c(self.schedules_c(), self.n_rules), self.rules_in(), t0, width,
+                                n_buckets, kind, avg, loc, mode, lock_ttl, lambda j: self.job_id(j).decode())
 
     def node_inflight(self, t0, width, n_buckets, loc=None, mode=_lib.EXCLUDE_NONE, engine=None):
         """Commands running per node at each bucket edge, each rule running

@@ -15,6 +15,12 @@ libcronsun_gpu.so (cg_jobset_*).
   JobSet.node_drops(t0, width, n_buckets)
                                    fires Job.limit() would drop per node and
                                    bucket, by each job's Parallels and AvgTime
+  JobSet.node_lock_skips(t0, width, n_buckets)
+                                   fires per node and bucket at which a
+                                   KindAlone / KindInterval job ran nowhere
+  JobSet.job_lock_runs(t0, width, n_buckets)
+                                   per exclusive job: its cluster-wide runs
+                                   and skipped fires per bucket
   JobSet.node_peak_rules(t0, width, n_buckets, k)
                                    per node: its peak, the bucket, and the k
                                    rules that contribute most to it
@@ -233,7 +239,8 @@ class JobSet(_Interned):
         and its ID is returned.  Commands started at or before t0 are not
         known (the first AvgTime over-admits), fires of one second are taken
         in rule order, and the KindAlone / KindInterval locks across nodes
-        are not modelled."""
+        are node_lock_skips', not this profile's (an alone job is limited per
+        node only here)."""
         from .engine import default_engine
         eng = engine or default_engine()
         rin = self.rules_in()
@@ -243,14 +250,52 @@ class JobSet(_Interned):
         return drops_of(self, eng, specs, rin, t0, width, n_buckets, dur, self.rule_parallels(), unit, loc, mode,
                         what), [self.jobs[j].ID for j in split]
 
+    def rule_kinds(self):
+        """(kind int32 [n_rules], avg_time_ms int64 [n_rules]): each rule's
+        job's Kind and AvgTime as stored (Engine.lock_runs' arguments)."""
+        return (np.array([self.jobs[j].Kind for j in self.rule_job], dtype=np.int32),
+                np.array([self.jobs[j].AvgTime for j in self.rule_job], dtype=np.int64))
+
+    def node_lock_skips(self, t0, width, n_buckets, loc=None, mode=_lib.EXCLUDE_NONE, lock_ttl=300, engine=None,
+                        what="skipped"):
+        """Fires per node and bucket at which a KindAlone / KindInterval job
+        ran on no node, because the job's etcd lock (one key per job, on all
+        nodes: job.go:235-271) was still held: {node ID: int64 [n_buckets]}
+        (Engine.lock_runs_per_node; what="granted": the fires at which the
+        node contends for a free lock -- an upper bound of its runs, since
+        which node wins is etcd arrival order).  A job is one unit whatever
+        its rules' node membership; a rule that runs on no node under the
+        exclude mode, or is replaced everywhere by a later rule with the same
+        Cmd key, does not contend.  Each run takes the job's AvgTime and
+        lock_ttl is conf.Config.LockTtl.  Locks held at t0 are not known
+        (cold start); clock skew, Parallels of an interval job, Retry and the
+        arrival order within a second are not reproduced."""
+        from .engine import default_engine
+        eng = engine or default_engine()
+        kind, avg = self.rule_kinds()
+        return lock_skips_of(self, eng, eng.upload(self.schedules()), self.rules_in(), t0, width, n_buckets, kind, avg,
+                             loc, mode, lock_ttl, what)
+
+    def job_lock_runs(self, t0, width, n_buckets, loc=None, mode=_lib.EXCLUDE_NONE, lock_ttl=300, engine=None):
+        """{job ID: (granted int64 [n_buckets], skipped int64 [n_buckets])}
+        for the KindAlone / KindInterval jobs, cluster-wide: the fires at which
+        the job runs (once, on whichever node wins the lock) and those at which
+        it runs nowhere -- the host sum of the job's rule rows of
+        Engine.lock_runs.  Limits as node_lock_skips."""
+        from .engine import default_engine
+        eng = engine or default_engine()
+        kind, avg = self.rule_kinds()
+        return job_lock_runs_of(eng, eng.upload(self.schedules()), self.rules_in(), t0, width, n_buckets, kind, avg,
+                                loc, mode, lock_ttl, lambda j: self.jobs[j].ID)
+
     def node_inflight(self, t0, width, n_buckets, loc=None, mode=_lib.EXCLUDE_NONE, engine=None):
         """Commands running per node at each bucket edge t0 + (b+1)*width
         (Engine.inflight_per_node), each rule running for its job's AvgTime
         (job.go:62): ({node ID: int64 [n_buckets]}, the number of rules that
         had no estimate and so count as never in flight).  Commands started at
         or before t0 are not counted and every fire is counted: the fires
-        Job.limit() would drop are node_drops', and the KindAlone /
-        KindInterval locks are not modelled."""
+        Job.limit() would drop are node_drops', those the KindAlone /
+        KindInterval locks skip node_lock_skips'."""
         from .engine import default_engine
         eng = engine or default_engine()
         rin = self.rules_in()
@@ -339,6 +384,48 @@ def drops_of(js, eng, specs, rin, t0, width, n_buckets, dur, par, unit, loc, mod
         drules.free()
         specs.free()
     return {js.node_id(n): counts[n] for n in range(rin.n_nodes)}
+
+
+def lock_units(rin):
+    """int32 [R] for Engine.lock_runs*: the job index per rule.  The lock key
+    is the job's ID, so a job is one unit whatever its rules' node membership
+    (unlike admission_units).  The rules of a job must be contiguous and the
+    jobs in order."""
+    unit = np.asarray(rin.rule_job[:rin.n_rules], dtype=np.int32)
+    if unit.size > 1 and (np.diff(unit) < 0).any():
+        raise ValueError("the rules of a job must be contiguous and the jobs in order")
+    return np.ascontiguousarray(unit)
+
+
+def lock_skips_of(js, eng, specs, rin, t0, width, n_buckets, kind, avg, loc, mode, lock_ttl, what):
+    """node_lock_skips of a job set: {node ID: int64 [B]} of the per-node lock profile."""
+    try:
+        contends = eng.rule_contends(rin, mode)
+        drules = eng.upload_rules(rin)
+        try:
+            counts = eng.lock_runs_per_node(specs, loc, t0, width, n_buckets, kind, avg, lock_units(rin), contends,
+                                            drules, mode, lock_ttl, what)
+        finally:
+            drules.free()
+    finally:
+        specs.free()
+    return {js.node_id(n): counts[n] for n in range(rin.n_nodes)}
+
+
+def job_lock_runs_of(eng, specs, rin, t0, width, n_buckets, kind, avg, loc, mode, lock_ttl, job_id):
+    """job_lock_runs of a job set: per exclusive job the sums of its rules'
+    GRANTED and SKIPPED rows."""
+    try:
+        unit, contends = lock_units(rin), eng.rule_contends(rin, mode)
+        rows = [eng.lock_runs(specs, loc, t0, width, n_buckets, kind, avg, unit, contends, lock_ttl, what)[0]
+                for what in ("granted", "skipped")]
+    finally:
+        specs.free()
+    out = {}
+    for j in np.unique(unit[np.asarray(kind) != KindCommon]).tolist():
+        mine = unit == j
+        out[job_id(j)] = tuple(r[mine].sum(axis=0, dtype=np.int64) for r in rows)
+    return out
 
 
 def peak_rules_of(js, eng, specs, rin, t0, width, n_buckets, k, dur, loc, mode, job_id, rule_id):

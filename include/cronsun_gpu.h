@@ -344,7 +344,9 @@ int cg_result_copy_offsets(cg_ctx* ctx, int64_t* host_offsets /* [R+1] */);
  * dispatcher wake: [9] scan, [10] due compaction, [11] advance; [13] the last
  * cg_dispatcher_fanout; of the last profile call (starts or in flight): [14] rule matrix, [15]
  * walked runs, [16] totals, [17] join + transpose (when rebuilt), [18] node
- * matrix.  n = entries written. */
+ * matrix; of the last admission or lock profile: [19] the pass that zeroes the
+ * rewritten rows, [20] the admission unit walk, [21] the lock unit walk (22
+ * entries in all).  n = entries written. */
 int cg_last_kernel_times(cg_ctx* ctx, float* ms, int n);
 /* Expansion phase timing: 2 (default) = a HIP event between every phase;
  * 1 = events around k_write_cf only ([3]; [0..2], [4], [5] read -1).  Events
@@ -648,9 +650,10 @@ int cg_profile_copy_nodes(cg_ctx* ctx, int32_t first_node, int32_t count, int64_
  *                     mode (the start profile's join); every node a rule is
  *                     scheduled on is counted, as the start profile counts
  *                     Cmd.Run calls
- * Not reproduced: the KindAlone / KindInterval locks -- a command the
- * reference would not start is counted.  (Job.Parallels drops are the
- * admission profile's, below; this profile counts every fire.)
+ * Not reproduced here: this profile counts every fire, also one the
+ * reference would not start.  (Job.Parallels drops are the admission
+ * profile's and the fires the KindAlone / KindInterval locks skip the lock
+ * profile's, both below.)
  * Consequences that hold exactly: dur_ms[r] == 0 gives a zero row; d_r ==
  * width the start profile's row; d_r == m * width the sliding sum of m start
  * buckets; d_r >= n_buckets * width the prefix sums of the start row (d_r is
@@ -714,8 +717,9 @@ int cg_inflight_per_node_device(cg_ctx* ctx, const cg_specs* specs, const cg_zon
  *     therefore over-admit, which is the in-flight profile's ramp.
  *   - The reference's counter is racy for fires of the same second
  *     (job.go:170-171).  Here rule order decides.
- *   - The etcd locks of KindAlone / KindInterval across nodes are still not
- *     modelled.  An alone job is limited per node only.
+ *   - The etcd locks of KindAlone / KindInterval across nodes are the lock
+ *     profile's, below, not this one's.  An alone job is limited per node only
+ *     here.
  *   - Actual run times differ from AvgTime.
  *
  * A unit with P == 0, d == 0 or P >= k*d (k its rule count: at most one fire
@@ -753,9 +757,113 @@ int cg_admit_per_node_device(cg_ctx* ctx, const cg_specs* specs, const cg_zone* 
                              const int64_t* parallels /* host, [R] */,
                              const int32_t* unit /* host, [R]; may be NULL */, int what, const cg_rules* rules,
                              int mode);
-/* *kind = CG_PROFILE_STARTS, CG_PROFILE_INFLIGHT, CG_PROFILE_ADMITTED or
- * CG_PROFILE_DROPPED: what the readable profile holds.  CG_EINVAL when no
- * profile is readable. */
+/* ----------------------------------------------------------- lock profile --- */
+/* Which fires of a KindAlone / KindInterval job run at all.  Cmd.Run, after
+ * limit(), calls lock() for Kind != KindCommon (job.go:134-147): it grants a
+ * lease of lockTtl() seconds and creates the key conf.Config.Lock + Job.ID only
+ * if it does not exist (job.go:235-271, client.go:95-109).  The key is the
+ * job's ID: one lock for all rules of the job, on all nodes.  Scheduled on m
+ * nodes, such a job runs once per fire, or not at all:
+ *   KindInterval  no keep-alive, and unlock() returns at once: the key lives
+ *                 ttl seconds from the grant, however long the command runs
+ *   KindAlone     keepAlive refreshes the lease while the command runs, and
+ *                 unlock() does not revoke it but calls KeepAliveOnce: the key
+ *                 lives until ttl seconds after the command ends
+ * with ttl = lockTtl() computed at the fire from the rule's next two fires
+ * (cg_lock_ttl_batch reproduces it).
+ *
+ * Buckets, t0, w = width, B = n_buckets <= 4096, t1 = t0 + B*w, the expansion
+ * over (t0, t1], @every anchored at t0 and the stuck-rule failure (CG_ERANGE
+ * before any cell is computed) are the start profile's.
+ *
+ * Inputs, all host arrays [R] owned by the caller, copied inside the call and
+ * not retained:
+ *   kind[r]         CG_JOB_COMMON, CG_JOB_ALONE or CG_JOB_INTERVAL
+ *   avg_time_ms[r]  Job.AvgTime as stored; it may be negative (lockTtl has a
+ *                   defined result for that).  d_r = ceil(max(avg, 0) / 1000),
+ *                   clamped to B*w; the clamp changes nothing inside the horizon
+ *   unit[r]         an int32 that does not decrease along r; NULL: every rule
+ *                   is its own unit.  All rules of a unit carry the same kind
+ *                   and avg_time_ms, else CG_EINVAL naming the first rule that
+ *                   differs.  A unit is the job, cluster-wide: the lock key is
+ *                   Job.ID, so differing node membership does not split a unit
+ *                   (unlike admission)
+ *   contends[r]     uint8; NULL: all ones.  0: the rule reaches no lock -- it is
+ *                   scheduled on no node under the exclude mode, or replaced
+ *                   everywhere by a later rule with the same Cmd key
+ *   lock_ttl        conf.Config.LockTtl as in cg_lock_ttl_batch; < 2 is
+ *                   CG_EINVAL (conf.go:136-138 never yields less)
+ *
+ * The literal process.  A lock unit is a unit with kind != COMMON.  Take the
+ * fires of its contending rules in (t0, t1] in order (time ascending, rule
+ * index ascending).  The state is free_at, initially -infinity.  For a fire
+ * (t, r):
+ *   1. If t < free_at, the fire is SKIPPED.
+ *   2. Otherwise ttl = lockTtl from Next_r(t) and Next_r(Next_r(t)), kind, avg
+ *      and lock_ttl: exactly what cg_lock_ttl_batch returns for now = t.  For
+ *      @every D, Next_r(x) = x + D.  Both Next calls may lie past t1; they are
+ *      not read off the expansion.
+ *   3. If ttl == 0, the fire is skipped and the state is unchanged (lock()
+ *      returns nil, job.go:246-248).
+ *   4. If either Next never returns (CG_NO_PROGRESS), the call fails with
+ *      CG_ERANGE naming the rule and no profile is readable afterwards.
+ *   5. Otherwise the fire is GRANTED, and free_at = t + ttl for INTERVAL or
+ *      t + d_r + ttl for ALONE.  (In ms the lease ends at t*1000 + max(avg, 0)
+ *      + ttl*1000; for whole-second fires that is the same test.)  A fire at
+ *      the very second the lease ends is granted.
+ *   granted[r][b] + skipped[r][b] == the start profile, for every cell
+ * Rows of COMMON units and of non-contending rules: granted is the start row,
+ * skipped is zero.
+ *
+ * `what` is CG_PROFILE_LOCK_GRANTED or CG_PROFILE_LOCK_SKIPPED and selects the
+ * rule matrix; cg_profile_kind reports it.  The call is a profile call: it
+ * replaces the readable profile, and bucket totals, the node matrix,
+ * cg_profile_result_device, cg_profile_copy_*, cg_profile_node_peaks and
+ * cg_profile_top_rules_* serve it unchanged.
+ *   - The SKIPPED node row is exact: the fires of node n's Cmds at which the
+ *     job ran on no node.
+ *   - The GRANTED node row is an upper bound: the fires at which node n
+ *     contends for a free lock.  It runs them iff it wins; which node wins is
+ *     etcd arrival order, not modelled and not decidable.
+ *   - The GRANTED bucket totals count each cluster-wide run once.
+ *
+ * Not reproduced:
+ *   - Locks held at t0 are unknown (cold start).
+ *   - Node clock skew.
+ *   - `now` is taken as t; the reference reads the clock a little later in the
+ *     same second.
+ *   - Parallels of an INTERVAL job: limit() runs before lock() on each node,
+ *     and whether the winner was saturated depends on who wins.  (For ALONE,
+ *     limit() is subsumed: the lock is held while any instance runs.)
+ *   - Job.Retry / Interval, which lengthen a run.
+ *   - Actual run times differ from AvgTime.
+ *   - Fires of one second are taken in rule order.
+ *
+ * All argument checks run before any device work, and the previous profile
+ * stays readable: NULL kind or avg_time_ms with R > 0, a kind that is none of
+ * the three, a decreasing unit, a mixed unit (each CG_EINVAL naming the first
+ * such rule), lock_ttl < 2, `what` not 4 or 5.  The zone table of the call
+ * reaches from the zero time to 12 years past t1, as cg_lock_ttl_batch's; if
+ * it, the plan and the walked runs' remembered positions (10 KiB) do not fit
+ * the 64 KiB of LDS the call fails with CG_ERANGE.
+ * cg_last_kernel_times [14..18] as the start profile's, [19] the pass that
+ * zeroes the rewritten rows, [21] the unit walk (k_lock_units); [20] is 0. */
+#define CG_PROFILE_LOCK_GRANTED 4
+#define CG_PROFILE_LOCK_SKIPPED 5
+int cg_lock_profile_device(cg_ctx* ctx, const cg_specs* specs, const cg_zone* z, int64_t t0, int64_t width,
+                           int32_t n_buckets, const int32_t* kind /* host, [R] */,
+                           const int64_t* avg_time_ms /* host, [R] */,
+                           const int32_t* unit /* host, [R]; may be NULL */,
+                           const uint8_t* contends /* host, [R]; may be NULL */, int64_t lock_ttl, int what);
+int cg_lock_profile_per_node_device(cg_ctx* ctx, const cg_specs* specs, const cg_zone* z, int64_t t0,
+                                    int64_t width, int32_t n_buckets, const int32_t* kind /* host, [R] */,
+                                    const int64_t* avg_time_ms /* host, [R] */,
+                                    const int32_t* unit /* host, [R]; may be NULL */,
+                                    const uint8_t* contends /* host, [R]; may be NULL */, int64_t lock_ttl,
+                                    int what, const cg_rules* rules, int mode);
+/* *kind = CG_PROFILE_STARTS, CG_PROFILE_INFLIGHT, CG_PROFILE_ADMITTED,
+ * CG_PROFILE_DROPPED, CG_PROFILE_LOCK_GRANTED or CG_PROFILE_LOCK_SKIPPED: what
+ * the readable profile holds.  CG_EINVAL when no profile is readable. */
 int cg_profile_kind(cg_ctx* ctx, int* kind);
 /* Per node row [first_node, first_node + count) of the last profile's node
  * matrix (of either kind): its largest cell and the first bucket attaining it;

@@ -489,6 +489,9 @@ const (
 	ProfileInFlight = C.CG_PROFILE_INFLIGHT
 	ProfileAdmitted = C.CG_PROFILE_ADMITTED
 	ProfileDropped  = C.CG_PROFILE_DROPPED
+	// the two kinds of LockProfile / LockProfilePerNode
+	ProfileLockGranted = C.CG_PROFILE_LOCK_GRANTED
+	ProfileLockSkipped = C.CG_PROFILE_LOCK_SKIPPED
 )
 
 // durations checks one duration per rule and returns the pointer C reads
@@ -510,7 +513,7 @@ func durations(durMs []int64, nRules int) (*C.int64_t, error) {
 // rounded up (not lockTtl's cost, which rounds down); totals[b] are the column
 // sums.  Commands started at or before t0 are not counted, so a row ramps up
 // over its first d seconds; every fire is counted (the fires Job.limit drops
-// are Admit's) and the KindAlone / KindInterval locks are not modelled.  Like the rest of this file it has not been
+// are Admit's, those the KindAlone / KindInterval locks skip LockProfile's).  Like the rest of this file it has not been
 // compiled here; tests/native/abi_inflight_c.c runs the same calls from C.
 func (e *Engine) InFlight(sp *Specs, z *Zone, t0 time.Time, width time.Duration, nBuckets int, durMs []int64) (inFlight []int32, totals []int64, err error) {
 	defer runtime.KeepAlive(e)
@@ -598,7 +601,8 @@ func admitArgs(parallels []int64, unit []int32, nRules int) (*C.int64_t, *C.int3
 // fewer than parallels[r] admitted fires a of the unit have a + d > t, d =
 // durMs[r]/1000 rounded up; parallels 0 is unlimited.  Commands started at or
 // before t0 are unknown, fires of one second are taken in rule order, and the
-// KindAlone / KindInterval locks across nodes are not modelled.  Not compiled
+// KindAlone / KindInterval locks across nodes are LockProfile's, not this
+// call's (an alone job is limited per node only here).  Not compiled
 // here; tests/native/abi_admit_c.c runs the same calls from C.
 func (e *Engine) Admit(sp *Specs, z *Zone, t0 time.Time, width time.Duration, nBuckets int, durMs, parallels []int64, unit []int32, what int) (counts []int32, totals []int64, err error) {
 	defer runtime.KeepAlive(e)
@@ -672,8 +676,117 @@ func (e *Engine) AdmitPerNode(sp *Specs, z *Zone, t0 time.Time, width time.Durat
 	return nodes, totals, nil
 }
 
+// lockArgs checks one Kind and AvgTime per rule and (unless nil) one unit and
+// one contends flag per rule, and returns the pointers C reads.
+func lockArgs(kind []int32, avgMs []int64, unit []int32, contends []uint8, nRules int) (*C.int32_t, *C.int64_t, *C.int32_t, *C.uint8_t, error) {
+	if len(kind) != nRules || len(avgMs) != nRules {
+		return nil, nil, nil, nil, fmt.Errorf("gpu: %d kinds and %d AvgTimes for %d rules", len(kind), len(avgMs), nRules)
+	}
+	if unit != nil && len(unit) != nRules {
+		return nil, nil, nil, nil, fmt.Errorf("gpu: %d units for %d rules", len(unit), nRules)
+	}
+	if contends != nil && len(contends) != nRules {
+		return nil, nil, nil, nil, fmt.Errorf("gpu: %d contends flags for %d rules", len(contends), nRules)
+	}
+	if nRules == 0 {
+		return nil, nil, nil, nil, nil
+	}
+	var u *C.int32_t
+	if unit != nil {
+		u = (*C.int32_t)(unsafe.Pointer(&unit[0]))
+	}
+	var c *C.uint8_t
+	if contends != nil {
+		c = (*C.uint8_t)(unsafe.Pointer(&contends[0]))
+	}
+	return (*C.int32_t)(unsafe.Pointer(&kind[0])), (*C.int64_t)(unsafe.Pointer(&avgMs[0])), u, c, nil
+}
+
+// LockProfile counts, per rule and bucket, the fires the etcd lock of a
+// KindAlone / KindInterval job (job.go:134-147, 235-271: one key per Job.ID,
+// for all its rules on all nodes) would grant (what = ProfileLockGranted) or
+// skip (ProfileLockSkipped).  kind[r] and avgMs[r] are the rule's job's Kind
+// and AvgTime as stored; unit[r] (non-decreasing; nil: every rule alone) the
+// job; contends[r] (nil: all) is 0 where the rule runs on no node; lockTtl is
+// conf.Config.LockTtl.  A lock unit's contending fires are taken in (time,
+// rule) order; one is skipped while t < free_at or when its lockTtl is 0, else
+// granted with free_at = t + ttl (interval) or t + ceil(AvgTime) + ttl
+// (alone), ttl being LockTtls at now = t.  Locks held at t0 are unknown, and
+// clock skew, Parallels of an interval job, Retry and the arrival order within
+// a second are not reproduced.  Not compiled here; tests/native/abi_lock_c.c
+// runs the same calls from C.
+func (e *Engine) LockProfile(sp *Specs, z *Zone, t0 time.Time, width time.Duration, nBuckets int, kind []int32, avgMs []int64, unit []int32, contends []uint8, lockTtl int64, what int) (counts []int32, totals []int64, err error) {
+	defer runtime.KeepAlive(e)
+	defer runtime.KeepAlive(sp)
+	defer runtime.KeepAlive(z)
+	defer runtime.KeepAlive(kind)
+	defer runtime.KeepAlive(avgMs)
+	defer runtime.KeepAlive(unit)
+	defer runtime.KeepAlive(contends)
+	k, a, u, c, err := lockArgs(kind, avgMs, unit, contends, sp.n)
+	if err != nil {
+		return nil, nil, err
+	}
+	if rc := C.cg_lock_profile_device(e.ctx, sp.s, z.z, C.int64_t(t0.Unix()), C.int64_t(width/time.Second),
+		C.int32_t(nBuckets), k, a, u, c, C.int64_t(lockTtl), C.int(what)); rc != 0 {
+		return nil, nil, lastErr(rc)
+	}
+	return e.profileRules(sp.n, nBuckets)
+}
+
+// LockProfilePerNode is LockProfile summed per node: node ID -> granted or
+// skipped fires per bucket over the rules that node runs (ProfilePerNode's
+// join).  The skipped row is exact: the fires of the node's Cmds at which the
+// job ran nowhere.  The granted row is an upper bound: the fires at which the
+// node contends for a free lock; which node wins is etcd arrival order.
+// totals are LockProfile's: each cluster-wide run once.
+func (e *Engine) LockProfilePerNode(sp *Specs, z *Zone, t0 time.Time, width time.Duration, nBuckets int, kind []int32, avgMs []int64, unit []int32, contends []uint8, lockTtl int64, what int, j *Jobset, mode int) (nodes map[string][]int64, totals []int64, err error) {
+	defer runtime.KeepAlive(e)
+	defer runtime.KeepAlive(sp)
+	defer runtime.KeepAlive(z)
+	defer runtime.KeepAlive(j)
+	defer runtime.KeepAlive(kind)
+	defer runtime.KeepAlive(avgMs)
+	defer runtime.KeepAlive(unit)
+	defer runtime.KeepAlive(contends)
+	k, a, u, c, err := lockArgs(kind, avgMs, unit, contends, sp.n)
+	if err != nil {
+		return nil, nil, err
+	}
+	var rin C.cg_rules_in
+	if rc := C.cg_jobset_rules(j.js, &rin); rc != 0 {
+		return nil, nil, lastErr(rc)
+	}
+	var r *C.cg_rules
+	if rc := C.cg_rules_upload(e.ctx, &rin, &r); rc != 0 {
+		return nil, nil, lastErr(rc)
+	}
+	defer C.cg_rules_free(r) // the node matrix stays in the engine's own buffers
+	if rc := C.cg_lock_profile_per_node_device(e.ctx, sp.s, z.z, C.int64_t(t0.Unix()), C.int64_t(width/time.Second),
+		C.int32_t(nBuckets), k, a, u, c, C.int64_t(lockTtl), C.int(what), r, C.int(mode)); rc != 0 {
+		return nil, nil, lastErr(rc)
+	}
+	nn := int(rin.n_nodes)
+	cnt := make([]int64, nn*nBuckets)
+	if len(cnt) > 0 {
+		if rc := C.cg_profile_copy_nodes(e.ctx, 0, C.int32_t(nn), (*C.int64_t)(unsafe.Pointer(&cnt[0]))); rc != 0 {
+			return nil, nil, lastErr(rc)
+		}
+	}
+	totals = make([]int64, nBuckets)
+	if rc := C.cg_profile_copy_totals(e.ctx, (*C.int64_t)(unsafe.Pointer(&totals[0]))); rc != 0 {
+		return nil, nil, lastErr(rc)
+	}
+	nodes = make(map[string][]int64, nn)
+	for n := 0; n < nn; n++ {
+		nodes[C.GoString(C.cg_jobset_node_id(j.js, C.int32_t(n)))] = cnt[n*nBuckets : (n+1)*nBuckets]
+	}
+	return nodes, totals, nil
+}
+
 // ProfileKind reports what the readable profile holds: ProfileStarts,
-// ProfileInFlight, ProfileAdmitted or ProfileDropped.
+// ProfileInFlight, ProfileAdmitted, ProfileDropped, ProfileLockGranted or
+// ProfileLockSkipped.
 func (e *Engine) ProfileKind() (int, error) {
 	defer runtime.KeepAlive(e)
 	var kind C.int
