@@ -35,6 +35,7 @@ NODE_ORDER_RULE, NODE_ORDER_TIME = 0, 1  # cg_set_node_order
 PROFILE_STARTS, PROFILE_INFLIGHT = 0, 1  # CG_PROFILE_*: cg_profile_kind
 PROFILE_ADMITTED, PROFILE_DROPPED = 2, 3  # the two kinds of cg_admit_*
 PROFILE_LOCK_GRANTED, PROFILE_LOCK_SKIPPED = 4, 5  # the two kinds of cg_lock_profile_*
+PROFILE_RUNNING, PROFILE_LOCK_RUNNING = 7, 8  # in flight after Job.limit() (cg_admit_*) / the job lock (cg_lock_profile_*)
 JOB_COMMON, JOB_ALONE, JOB_INTERVAL = 0, 1, 2  # CG_JOB_*: Job.Kind (job.go:30-34)
 ADMIT_MAX_PARALLELS = 16  # CG_ADMIT_MAX_PARALLELS: the largest limit of a unit that can drop
 CG_FANOUT_AUTO, CG_FANOUT_FILTER, CG_FANOUT_DUE = 0, 1, 2  # cg_dispatcher_set_fanout_path

@@ -252,7 +252,7 @@ struct cg_ctx {
   // in the first two), [19..20] the last admission profile's own kernels
   // (k_admit_prepare, k_admit_units; 0 after any other profile call), [21]
   // the last lock profile's unit walk (k_lock_units; its k_admit_prepare in [19])
-  float kt[22] = {0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0};
+  float kt[23] = {0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0};
   // expansion phase timing: 2 = an event between every phase (kt[0..5]);
   // 1 = events around k_write_cf only (kt[3]; the others read -1).  Each
   // event recorded between two kernels costs 6-12 us of idle GPU on this
@@ -386,7 +386,8 @@ struct cg_ctx {
   DBuf<uint8_t> pf_admit_flag;
   // k_lock_units lowers it from ~0 to a rule whose Next never returns (set before every launch)
   DBuf<unsigned long long> pf_lock_stuck;
-  hipEvent_t pfev[8] = {};  // created by the first profile call ([6], [7]: around k_admit_prepare; the unit walk ends at [2])
+  hipEvent_t pfev[9] = {};  // created by the first profile call ([6], [7]: around k_admit_prepare; the unit walk ends at [2],
+                            // in a RUNNING call at [8] with k_rows_prefix between [8] and [2])
   // The node matrix is summed over nt_off / nt_rule, which are the per-node
   // path's cache and may be rebuilt under a readable profile: nt_gen counts
   // the rebuilds (transpose_locked, and the dispatcher bind that takes the

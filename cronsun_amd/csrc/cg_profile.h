@@ -161,4 +161,30 @@ CG_HD void inflight_walk_row(const DSpec& sp, const ZoneView& z, const Segment* 
   }
 }
 
+// -------------------------------------------------------- running profile --
+// Commands in flight counting only the fires that start (the admitted fires of
+// cg_admit.h, the granted ones of cg_lock.h).  A fire a in (t0, t1] with a run
+// time of d whole seconds is in flight at the edges of buckets lo .. hi - 1
+// (e_b - d < a <= e_b), the range inflight_walk_row names; hi may lie past B.
+struct BucketRange {
+  int64_t lo, hi;
+};
+CG_HD BucketRange running_range(int64_t a, int64_t d, int64_t t0, int64_t w) {
+  return BucketRange{(a - t0 - 1) / w, (a + d - 1 - t0) / w};
+}
+
+// One started fire as a difference in the rule's own row: +1 where it comes
+// into flight, -1 at the first bucket whose edge it no longer reaches (none
+// when it runs past the last edge).  An inclusive prefix sum along the row
+// (k_rows_prefix; the host check's loop) turns the differences into the cells,
+// at 2 stores per fire rather than one per bucket it spans.  d == 0, or a run
+// that ends before the next edge, leaves nothing.
+CG_HD void running_emit_diff(int32_t* row, int32_t B, int64_t a, int64_t d, int64_t t0, int64_t w) {
+  if (a <= t0) return;
+  const BucketRange g = running_range(a, d, t0, w);
+  if (g.hi == g.lo || g.lo >= B) return;
+  row[g.lo] += 1;
+  if (g.hi < B) row[g.hi] -= 1;
+}
+
 }  // namespace cg

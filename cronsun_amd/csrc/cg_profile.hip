@@ -40,6 +40,15 @@
 //   k_lock_units      one lane per lock unit with a contending rule: walks the
 //                     unit's granted fires (cg_lock.h, lock_walk_unit) and adds
 //                     (GRANTED) or subtracts (SKIPPED) 1 in the rule's own row
+//
+// Running profile (CG_PROFILE_RUNNING / CG_PROFILE_LOCK_RUNNING): commands in
+// flight counting only the fires that start.  The in-flight chain's first two
+// kernels fill the rule matrix with every rule's d, then
+//   k_admit_prepare   zeroes the flagged rows
+//   k_admit_units / k_lock_units  in difference mode: +1 at the bucket a started
+//                     fire comes into flight, -1 where it has ended
+//                     (cg_profile.h, running_emit_diff)
+//   k_rows_prefix     in-place inclusive prefix sum along each flagged row
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
@@ -204,6 +213,8 @@ __global__ __launch_bounds__(256) void k_admit_prepare(const uint8_t* __restrict
 // are dense); a block is one wave.  The lane walks the unit's admitted fires
 // and adds `step` (+1 ADMITTED, -1 DROPPED: start - admitted) to the cell of
 // the firing rule's row -- rows belong to one unit, so plain read-modify-write.
+// With diff != 0 (RUNNING) it writes the fire's difference over its run time
+// u.d instead (cg_profile.h, running_emit_diff) and step is not read.
 // The ring of the last P admitted starts and the walked runs' remembered
 // positions (cg_admit.h) live in LDS behind the staged plan, [slot][lane]: a
 // lane's slots are 512 B (256 B) apart, conflict-free at any head.
@@ -214,7 +225,7 @@ __global__ __launch_bounds__(kAdmitBlock) void k_admit_units(const DSpec* __rest
                                                               const uint32_t* __restrict__ run_dmask,
                                                               const AdmitUnit* __restrict__ units, int64_t U,
                                                               size_t ring_off, int64_t w, int32_t B, int32_t step,
-                                                              int32_t* __restrict__ out) {
+                                                              int32_t diff, int32_t* __restrict__ out) {
   extern __shared__ __align__(16) char lds[];
   PlanView v = stage_plan(p, lds);
   // [ring 16][walk t 8] i64, then [rel 8][s 8][q 8] i32, each [slot][lane]
@@ -229,6 +240,10 @@ __global__ __launch_bounds__(kAdmitBlock) void k_admit_units(const DSpec* __rest
   const int64_t t0 = p.t0;
   admit_walk_unit(specs, v.z, v.segs, p.G, run_anchor, run_count, run_dmask, t0, p.t1, u, ring, kAdmitBlock, wc,
                   [&](int64_t r, int64_t t) {
+                    if (diff) {  // RUNNING: the fire's difference, summed by k_rows_prefix
+                      running_emit_diff(out + r * B, B, t, u.d, t0, w);
+                      return;
+                    }
                     const int64_t b = (t - t0 - 1) / w;
                     if (t > t0 && b < B) out[r * B + b] += step;
                   });
@@ -239,7 +254,8 @@ __global__ __launch_bounds__(kAdmitBlock) void k_admit_units(const DSpec* __rest
 // host so waves are dense); a block is one wave.  The lane walks the unit's
 // granted fires and adds `step` (+1 GRANTED, -1 SKIPPED: start - granted) to
 // the cell of the firing rule's row -- a row belongs to one unit, so plain
-// read-modify-write.  contends [R]: the prepare pass's flags, inside a lock
+// read-modify-write.  With diff != 0 (LOCK_RUNNING) it writes the fire's
+// difference over u.d instead, as k_admit_units does.  contends [R]: the prepare pass's flags, inside a lock
 // unit "this rule reaches the lock".  The walked runs' remembered positions
 // (cg_admit.h) live in LDS behind the staged plan, [slot][lane]; there is no
 // ring.  A rule whose Next never returns lowers *stuck to its index.
@@ -251,7 +267,7 @@ __global__ __launch_bounds__(kLockBlock) void k_lock_units(const DSpec* __restri
                                                             const LockUnit* __restrict__ units, int64_t U,
                                                             const uint8_t* __restrict__ contends, size_t cache_off,
                                                             int64_t lock_ttl, int64_t w, int32_t B, int32_t step,
-                                                            int32_t* __restrict__ out,
+                                                            int32_t diff, int32_t* __restrict__ out,
                                                             unsigned long long* __restrict__ stuck) {
   extern __shared__ __align__(16) char lds[];
   PlanView v = stage_plan(p, lds);
@@ -266,6 +282,10 @@ __global__ __launch_bounds__(kLockBlock) void k_lock_units(const DSpec* __restri
   const int64_t t0 = p.t0;
   const int64_t bad = lock_walk_unit(specs, v.z, v.segs, p.G, run_anchor, run_count, run_dmask, t0, p.t1, u, lock_ttl,
                                      contends, wc, [&](int64_t r, int64_t t) {
+                                       if (diff) {  // LOCK_RUNNING: the command runs u.d whatever its lease does
+                                         running_emit_diff(out + r * B, B, t, u.d, t0, w);
+                                         return;
+                                       }
                                        const int64_t b = (t - t0 - 1) / w;
                                        if (t > t0 && b < B) out[r * B + b] += step;
                                      });
@@ -350,6 +370,65 @@ __global__ __launch_bounds__(256) void k_profile_totals(const int32_t* __restric
   }
   const int64_t sum = tile_reduce(t, acc);
   if (int32_t(threadIdx.x) < t.W && t.col < B && sum != 0) atomicAdd(tot + t.col, (unsigned long long)sum);
+}
+
+// --------------------------------------------------------- running profile --
+// Inclusive scan of x over the 64 lanes of the wave, by DPP (no LDS round
+// trips): row_shr 1/2/4/8 inside each 16-lane row, row_bcast:15 adds the last
+// lane of rows 0 and 2 to rows 1 and 3, row_bcast:31 lane 31 to rows 2 and 3.
+// All 64 lanes must be active.
+__device__ __forceinline__ int32_t scan_wave(int32_t x) {
+  x += __builtin_amdgcn_update_dpp(0, x, 0x111, 0xf, 0xf, true);   // row_shr:1
+  x += __builtin_amdgcn_update_dpp(0, x, 0x112, 0xf, 0xf, true);   // row_shr:2
+  x += __builtin_amdgcn_update_dpp(0, x, 0x114, 0xf, 0xf, true);   // row_shr:4
+  x += __builtin_amdgcn_update_dpp(0, x, 0x118, 0xf, 0xf, true);   // row_shr:8
+  x += __builtin_amdgcn_update_dpp(0, x, 0x142, 0xa, 0xf, false);  // row_bcast:15 into rows 1, 3
+  x += __builtin_amdgcn_update_dpp(0, x, 0x143, 0xc, 0xf, false);  // row_bcast:31 into rows 2, 3
+  return x;
+}
+
+// In-place inclusive prefix sum along the buckets of every flagged row of the
+// rule matrix (flag [R]: the prepare pass's); other rows are neither read nor
+// written.  Every cell is stored once by the one lane that owns it, so the
+// result does not depend on the grid.  Rows are strided over the grid, 64-bit
+// cell index.
+//   B >= 64  one wave per row (the flag is wave-uniform: an unflagged row costs
+//            one byte), 64-cell chunks loaded coalesced; the next chunk's load
+//            is issued before the current chunk's scan, the carry is lane 63's
+//            result of the previous chunk
+//   B < 64   tile_lane's (slot, col): 64 / B rows side by side in a wave, a
+//            Hillis-Steele scan in which a lane takes only from lanes of its
+//            own slot (col >= offset); B need not be a power of two
+__global__ __launch_bounds__(256) void k_rows_prefix(const uint8_t* __restrict__ flag, int64_t R, int32_t B,
+                                                      int32_t* __restrict__ out) {
+  if (B >= 64) {
+    const int32_t lane = threadIdx.x & 63;
+    for (int64_t r = int64_t(blockIdx.x) * 4 + (threadIdx.x >> 6); r < R; r += int64_t(gridDim.x) * 4) {
+      if (!flag[r]) continue;  // a whole wave
+      int32_t* row = out + r * B;
+      int32_t carry = 0, next = row[lane];
+      for (int32_t c0 = 0; c0 < B; c0 += 64) {
+        const int32_t i = c0 + lane;
+        int32_t x = next;
+        next = i + 64 < B ? row[i + 64] : 0;
+        x = scan_wave(x) + carry;  // lanes past B hold 0: lane 63 has the row's sum so far
+        if (i < B) row[i] = x;
+        carry = __builtin_amdgcn_readlane(x, 63);
+      }
+    }
+    return;
+  }
+  const TileLane t = tile_lane(B);  // (gridDim.y == 1: col is the bucket)
+  for (int64_t r0 = int64_t(blockIdx.x) * t.slots; r0 < R; r0 += int64_t(gridDim.x) * t.slots) {
+    const int64_t r = r0 + t.slot;
+    const bool mine = t.active && r < R && flag[r] != 0;
+    int32_t x = mine ? out[r * B + t.col] : 0;
+    for (int32_t o = 1; o < B; o <<= 1) {  // every lane shuffles; only its own slot's lanes feed it
+      const int32_t y = __shfl_up(x, o, 64);
+      if (t.col >= o) x += y;
+    }
+    if (mine) out[r * B + t.col] = x;
+  }
 }
 
 // chunks of kNodeChunk rules a node's list is cut into (a node without rules
@@ -440,14 +519,21 @@ int ensure_events(cg_ctx* c) {
 // drains it); c->mu held.  pfev[0..3] bracket the three kernels (pfev[3]:
 // the end of the totals, where a per-node call's join starts).  dsec: null for
 // the start profile, else the in-flight profile's durations (host, [R], whole
-// seconds clamped to B * w), uploaded here and read by this call's kernels only.
+// seconds clamped to B * w), uploaded here and read by this call's kernels only;
+// it comes together with adm or lk in a RUNNING call, whose base rows are the
+// in-flight profile's and whose unit walk writes differences that k_rows_prefix
+// sums (pfev[8]: the end of that walk; pfev[2] then follows the prefix).
 // An admission call's checked arguments: the units that can drop, compacted,
 // and per rule whether its unit is one of them.  Host memory that outlives the
 // stream synchronise that ends the call.
+// RUNNING kinds also carry every rule's d (dsec, as an in-flight call's).
 struct AdmitCall {
   int what = CG_PROFILE_ADMITTED;
   std::vector<AdmitUnit> units;
   std::vector<uint8_t> flag;
+  std::vector<int64_t> dsec;
+  bool running() const { return what == CG_PROFILE_RUNNING; }
+  const std::vector<int64_t>* durations() const { return running() ? &dsec : nullptr; }
 };
 // A lock call's: the lock units with a contending rule, compacted, and per
 // rule whether it is a contending rule of a lock unit.
@@ -456,6 +542,9 @@ struct LockCall {
   int64_t lock_ttl = 0;
   std::vector<LockUnit> units;
   std::vector<uint8_t> flag;
+  std::vector<int64_t> dsec;
+  bool running() const { return what == CG_PROFILE_LOCK_RUNNING; }
+  const std::vector<int64_t>* durations() const { return running() ? &dsec : nullptr; }
 };
 
 int profile_rules_enqueue(cg_ctx* c, const cg_specs* s, const cg_zone* z, int64_t t0, int64_t w, int32_t B,
@@ -474,8 +563,12 @@ int profile_rules_enqueue(cg_ctx* c, const cg_specs* s, const cg_zone* z, int64_
     return rc;
   hipStream_t st = c->st;
   HIPCHK(hipMemsetAsync(c->pf_totals.p, 0, size_t(B) * 8, st));
-  for (int i = 14; i < 22; i++) c->kt[i] = 0.f;
-  for (int i : {0, 1, 6, 7, 2, 3}) (void)hipEventRecord(c->pfev[i], st);
+  for (int i = 14; i < 23; i++) c->kt[i] = 0.f;
+  const bool running = (adm && adm->running()) || (lk && lk->running());
+  hipEvent_t walk_end = c->pfev[running ? 8 : 2];
+  for (int i : {0, 1, 6, 7}) (void)hipEventRecord(c->pfev[i], st);
+  if (running) (void)hipEventRecord(walk_end, st);
+  for (int i : {2, 3}) (void)hipEventRecord(c->pfev[i], st);
   if (!empty) {
     RunSet& rs = c->rs;
     // a rule whose reference loop never ends: refuse before any cell is computed
@@ -519,13 +612,13 @@ int profile_rules_enqueue(cg_ctx* c, const cg_specs* s, const cg_zone* z, int64_
         HIPCHK(hipMemcpyAsync(c->pf_admit_units.p, adm->units.data(), size_t(U) * sizeof(AdmitUnit), hipMemcpyHostToDevice, st));
       (void)hipEventRecord(c->pfev[6], st);
       hipLaunchKernelGGL(k_admit_prepare, dim3(gridn(R * B, 256, 4096)), dim3(256), 0, st, c->pf_admit_flag.p, R, B,
-                         adm->what == CG_PROFILE_ADMITTED ? 1 : 0, c->pf_rules.p);
+                         adm->what != CG_PROFILE_DROPPED ? 1 : 0, c->pf_rules.p);
       (void)hipEventRecord(c->pfev[7], st);
       if (U > 0)
         hipLaunchKernelGGL(k_admit_units, dim3(unsigned((U + kAdmitBlock - 1) / kAdmitBlock)), dim3(kAdmitBlock), admit_lds,
                            st, s->d, rs.pa, rs.run_anchor.p, rs.run_count.p, rs.run_dmask.p,
                            reinterpret_cast<const AdmitUnit*>(c->pf_admit_units.p), U, ring_off, w, B,
-                           adm->what == CG_PROFILE_ADMITTED ? 1 : -1, c->pf_rules.p);
+                           adm->what == CG_PROFILE_DROPPED ? -1 : 1, running ? 1 : 0, c->pf_rules.p);
     }
     if (lk) {
       const int64_t U = int64_t(lk->units.size());
@@ -539,15 +632,15 @@ int profile_rules_enqueue(cg_ctx* c, const cg_specs* s, const cg_zone* z, int64_
       HIPCHK(hipMemsetAsync(c->pf_lock_stuck.p, 0xFF, sizeof(unsigned long long), st));
       (void)hipEventRecord(c->pfev[6], st);
       hipLaunchKernelGGL(k_admit_prepare, dim3(gridn(R * B, 256, 4096)), dim3(256), 0, st, c->pf_admit_flag.p, R, B,
-                         lk->what == CG_PROFILE_LOCK_GRANTED ? 1 : 0, c->pf_rules.p);
+                         lk->what != CG_PROFILE_LOCK_SKIPPED ? 1 : 0, c->pf_rules.p);
       (void)hipEventRecord(c->pfev[7], st);
       if (U > 0)
         hipLaunchKernelGGL(k_lock_units, dim3(unsigned((U + kLockBlock - 1) / kLockBlock)), dim3(kLockBlock), lock_lds, st,
                            s->d, rs.pa, rs.run_anchor.p, rs.run_count.p, rs.run_dmask.p,
                            reinterpret_cast<const LockUnit*>(c->pf_admit_units.p), U, c->pf_admit_flag.p, cache_off,
-                           lk->lock_ttl, w, B, lk->what == CG_PROFILE_LOCK_GRANTED ? 1 : -1, c->pf_rules.p,
-                           c->pf_lock_stuck.p);
-      (void)hipEventRecord(c->pfev[2], st);
+                           lk->lock_ttl, w, B, lk->what == CG_PROFILE_LOCK_SKIPPED ? -1 : 1, running ? 1 : 0,
+                           c->pf_rules.p, c->pf_lock_stuck.p);
+      (void)hipEventRecord(walk_end, st);
       HIPCHK(hipGetLastError());
       // a granted fire whose Next never returns: the reference hangs in
       // lockTtl there, and the unit's rows are unfinished -- no profile
@@ -559,6 +652,15 @@ int profile_rules_enqueue(cg_ctx* c, const cg_specs* s, const cg_zone* z, int64_
                                       ": Next never returns from a fire of this horizon that finds the lock free "
                                       "(the reference's lockTtl does not return there)");
     } else {
+      (void)hipEventRecord(walk_end, st);
+    }
+    if (running) {
+      // the flagged rows hold differences: sum them along the buckets (rows of
+      // a call without a unit to walk are all unflagged)
+      const int rows_per_block = B >= 64 ? 4 : 4 * (64 / B);
+      if ((adm ? adm->units.size() : lk->units.size()) > 0)
+        hipLaunchKernelGGL(k_rows_prefix, dim3(gridn(R, rows_per_block, 4096)), dim3(256), 0, st, c->pf_admit_flag.p, R,
+                           B, c->pf_rules.p);
       (void)hipEventRecord(c->pfev[2], st);
     }
     hipLaunchKernelGGL(k_profile_totals, dim3(gridn(R, kTotalChunk, 1 << 30), (B + 63) / 64), dim3(256), 0, st,
@@ -575,17 +677,21 @@ int profile_rules_enqueue(cg_ctx* c, const cg_specs* s, const cg_zone* z, int64_
 
 void profile_rule_times(cg_ctx* c) {
   for (int i = 0; i < 3; i++) (void)hipEventElapsedTime(&c->kt[14 + i], c->pfev[i], c->pfev[i + 1]);
-  if (c->pf_kind == CG_PROFILE_ADMITTED || c->pf_kind == CG_PROFILE_DROPPED) {
+  const bool running = c->pf_kind == CG_PROFILE_RUNNING || c->pf_kind == CG_PROFILE_LOCK_RUNNING;
+  hipEvent_t walk_end = c->pfev[running ? 8 : 2];
+  if (c->pf_kind == CG_PROFILE_ADMITTED || c->pf_kind == CG_PROFILE_DROPPED || c->pf_kind == CG_PROFILE_RUNNING) {
     // the admission kernels sit between the walked runs and the totals
     (void)hipEventElapsedTime(&c->kt[15], c->pfev[1], c->pfev[6]);
     (void)hipEventElapsedTime(&c->kt[19], c->pfev[6], c->pfev[7]);
-    (void)hipEventElapsedTime(&c->kt[20], c->pfev[7], c->pfev[2]);
+    (void)hipEventElapsedTime(&c->kt[20], c->pfev[7], walk_end);
   }
-  if (c->pf_kind == CG_PROFILE_LOCK_GRANTED || c->pf_kind == CG_PROFILE_LOCK_SKIPPED) {
+  if (c->pf_kind == CG_PROFILE_LOCK_GRANTED || c->pf_kind == CG_PROFILE_LOCK_SKIPPED ||
+      c->pf_kind == CG_PROFILE_LOCK_RUNNING) {
     (void)hipEventElapsedTime(&c->kt[15], c->pfev[1], c->pfev[6]);
     (void)hipEventElapsedTime(&c->kt[19], c->pfev[6], c->pfev[7]);
-    (void)hipEventElapsedTime(&c->kt[21], c->pfev[7], c->pfev[2]);
+    (void)hipEventElapsedTime(&c->kt[21], c->pfev[7], walk_end);
   }
+  if (running) (void)hipEventElapsedTime(&c->kt[22], c->pfev[8], c->pfev[2]);  // k_rows_prefix
   // the count and scan behind it, when the chain recorded their events ([0], [1])
   if (c->phase_timing >= 2 && c->pf_R > 0) {
     (void)hipEventElapsedTime(&c->kt[0], c->ev[0], c->ev[1]);
@@ -629,8 +735,8 @@ int profile_call(cg_ctx* c, const cg_specs* s, const cg_zone* z, int64_t t0, int
 int admit_units(const char* what_fn, const cg_specs* s, const int64_t* dur_ms, const int64_t* parallels,
                 const int32_t* unit, int what, int64_t horizon, AdmitCall* out) {
   const std::string fn(what_fn);
-  if (what != CG_PROFILE_ADMITTED && what != CG_PROFILE_DROPPED)
-    return cg_fail(CG_EINVAL, fn + ": what must be CG_PROFILE_ADMITTED or CG_PROFILE_DROPPED");
+  if (what != CG_PROFILE_ADMITTED && what != CG_PROFILE_DROPPED && what != CG_PROFILE_RUNNING)
+    return cg_fail(CG_EINVAL, fn + ": what must be CG_PROFILE_ADMITTED, CG_PROFILE_DROPPED or CG_PROFILE_RUNNING");
   const int64_t R = int64_t(s->n);
   if (R > 0 && !dur_ms) return cg_fail(CG_EINVAL, fn + ": rule 0: null dur_ms");
   if (R > 0 && !parallels) return cg_fail(CG_EINVAL, fn + ": rule 0: null parallels");
@@ -643,6 +749,11 @@ int admit_units(const char* what_fn, const cg_specs* s, const int64_t* dur_ms, c
   out->what = what;
   out->units.clear();
   out->flag.assign(size_t(R), 0);
+  out->dsec.clear();
+  if (out->running()) {
+    out->dsec.resize(size_t(R));
+    for (int64_t r = 0; r < R; r++) out->dsec[size_t(r)] = inflight_seconds(dur_ms[r], horizon);
+  }
   for (int64_t r0 = 0; r0 < R;) {
     int64_t r1 = r0 + 1;
     if (unit)
@@ -670,8 +781,9 @@ int admit_units(const char* what_fn, const cg_specs* s, const int64_t* dur_ms, c
 int lock_units(const char* what_fn, const cg_specs* s, const int32_t* kind, const int64_t* avg_ms, const int32_t* unit,
                const uint8_t* contends, int64_t lock_ttl, int what, int64_t horizon, LockCall* out) {
   const std::string fn(what_fn);
-  if (what != CG_PROFILE_LOCK_GRANTED && what != CG_PROFILE_LOCK_SKIPPED)
-    return cg_fail(CG_EINVAL, fn + ": what must be CG_PROFILE_LOCK_GRANTED or CG_PROFILE_LOCK_SKIPPED");
+  if (what != CG_PROFILE_LOCK_GRANTED && what != CG_PROFILE_LOCK_SKIPPED && what != CG_PROFILE_LOCK_RUNNING)
+    return cg_fail(CG_EINVAL, fn + ": what must be CG_PROFILE_LOCK_GRANTED, CG_PROFILE_LOCK_SKIPPED or "
+                                   "CG_PROFILE_LOCK_RUNNING");
   if (lock_ttl < 2) return cg_fail(CG_EINVAL, fn + ": lock_ttl must be at least 2 (conf.go:136-138)");
   const int64_t R = int64_t(s->n);
   if (R > 0 && !kind) return cg_fail(CG_EINVAL, fn + ": rule 0: null kind");
@@ -687,6 +799,12 @@ int lock_units(const char* what_fn, const cg_specs* s, const int32_t* kind, cons
   out->lock_ttl = lock_ttl;
   out->units.clear();
   out->flag.assign(size_t(R), 0);
+  out->dsec.clear();
+  if (out->running()) {
+    out->dsec.resize(size_t(R));
+    for (int64_t r = 0; r < R; r++)
+      out->dsec[size_t(r)] = inflight_seconds(std::max<int64_t>(avg_ms[r], 0), horizon);
+  }
   for (int64_t r0 = 0; r0 < R;) {
     int64_t r1 = r0 + 1;
     if (unit)
@@ -818,7 +936,7 @@ int cg_admit_device(cg_ctx* c, const cg_specs* s, const cg_zone* z, int64_t t0, 
   if (int rc = profile_check_args("cg_admit_device", c, s, z, width, n_buckets)) return rc;
   if (int rc = admit_units("cg_admit_device", s, dur_ms, parallels, unit, what, int64_t(n_buckets) * width, &adm))
     return rc;
-  return profile_call(c, s, z, t0, width, n_buckets, nullptr, &adm);
+  return profile_call(c, s, z, t0, width, n_buckets, adm.durations(), &adm);
 }
 
 int cg_admit_per_node_device(cg_ctx* c, const cg_specs* s, const cg_zone* z, int64_t t0, int64_t width,
@@ -830,7 +948,7 @@ int cg_admit_per_node_device(cg_ctx* c, const cg_specs* s, const cg_zone* z, int
   if (int rc = admit_units("cg_admit_per_node_device", s, dur_ms, parallels, unit, what, int64_t(n_buckets) * width,
                            &adm))
     return rc;
-  return profile_per_node_call(c, s, z, t0, width, n_buckets, rules, mode, nullptr, &adm);
+  return profile_per_node_call(c, s, z, t0, width, n_buckets, rules, mode, adm.durations(), &adm);
 }
 
 int cg_lock_profile_device(cg_ctx* c, const cg_specs* s, const cg_zone* z, int64_t t0, int64_t width,
@@ -841,7 +959,7 @@ int cg_lock_profile_device(cg_ctx* c, const cg_specs* s, const cg_zone* z, int64
   if (int rc = lock_units("cg_lock_profile_device", s, kind, avg_time_ms, unit, contends, lock_ttl, what,
                           int64_t(n_buckets) * width, &lk))
     return rc;
-  return profile_call(c, s, z, t0, width, n_buckets, nullptr, nullptr, &lk);
+  return profile_call(c, s, z, t0, width, n_buckets, lk.durations(), nullptr, &lk);
 }
 
 int cg_lock_profile_per_node_device(cg_ctx* c, const cg_specs* s, const cg_zone* z, int64_t t0, int64_t width,
@@ -854,7 +972,7 @@ int cg_lock_profile_per_node_device(cg_ctx* c, const cg_specs* s, const cg_zone*
   if (int rc = lock_units("cg_lock_profile_per_node_device", s, kind, avg_time_ms, unit, contends, lock_ttl, what,
                           int64_t(n_buckets) * width, &lk))
     return rc;
-  return profile_per_node_call(c, s, z, t0, width, n_buckets, rules, mode, nullptr, nullptr, &lk);
+  return profile_per_node_call(c, s, z, t0, width, n_buckets, rules, mode, lk.durations(), nullptr, &lk);
 }
 
 int cg_profile_kind(cg_ctx* c, int* kind) {

@@ -894,13 +894,14 @@ class Engine:
         return self._profile_tensors()
 
     # ------------------------------------------------ admission profile
-    _ADMIT_WHAT = {"admitted": _lib.PROFILE_ADMITTED, "dropped": _lib.PROFILE_DROPPED}
+    _ADMIT_WHAT = {"admitted": _lib.PROFILE_ADMITTED, "dropped": _lib.PROFILE_DROPPED,
+                   "running": _lib.PROFILE_RUNNING}
 
     def _admit_args(self, n, dur_ms, parallels, unit, what):
         """Checked host arrays of an admission call: (dur_ms, parallels, unit
         pointer or None, CG_PROFILE_*), plus the arrays to keep alive."""
         if what not in self._ADMIT_WHAT:
-            raise ValueError(f"what must be 'admitted' or 'dropped', got {what!r}")
+            raise ValueError(f"what must be 'admitted', 'dropped' or 'running', got {what!r}")
         d = self._durations(dur_ms, n)
         p = np.ascontiguousarray(parallels, dtype=np.int64)
         if p.shape != (n,):
@@ -922,7 +923,11 @@ class Engine:
         must share dur_ms and parallels.  A unit's fires are taken in (time,
         rule) order; one is admitted while fewer than parallels admitted
         fires a of the unit have a + d > t.  Commands started at or before t0
-        are not known, so the first d seconds over-admit."""
+        are not known, so the first d seconds over-admit.  what="running":
+        the commands in flight at each bucket edge e_b = t0 + (b+1)*width
+        counting only the admitted fires a (e_b - d < a <= e_b) -- inflight()
+        less the fires that never start; a unit's cells sum to at most its
+        parallels at every edge."""
         sp = self._specs(specs)
         d, p, u, w = self._admit_args(sp.n, dur_ms, parallels, unit, what)
         check(lib().cg_admit_device(self._h, sp._h, self._loc(loc).handle, int(t0), int(width), int(n_buckets),
@@ -959,13 +964,14 @@ class Engine:
         return list(buf)[19:21]
 
     # ------------------------------------------------------ lock profile
-    _LOCK_WHAT = {"granted": _lib.PROFILE_LOCK_GRANTED, "skipped": _lib.PROFILE_LOCK_SKIPPED}
+    _LOCK_WHAT = {"granted": _lib.PROFILE_LOCK_GRANTED, "skipped": _lib.PROFILE_LOCK_SKIPPED,
+                  "running": _lib.PROFILE_LOCK_RUNNING}
 
     def _lock_args(self, n, kind, avg_time_ms, unit, contends, lock_ttl, what):
         """Checked host arrays of a lock call: (kind int32, avg_time_ms int64,
         unit int32 or None, contends uint8 or None, lock_ttl, CG_PROFILE_*)."""
         if what not in self._LOCK_WHAT:
-            raise ValueError(f"what must be 'granted' or 'skipped', got {what!r}")
+            raise ValueError(f"what must be 'granted', 'skipped' or 'running', got {what!r}")
         k = np.ascontiguousarray(kind, dtype=np.int32)
         if k.shape != (n,):
             raise ValueError(f"kind must hold one Job.Kind per rule ({n}), got shape {k.shape}")
@@ -1003,7 +1009,11 @@ class Engine:
         t < free_at or when its lockTtl is 0, else granted with free_at = t +
         ttl (INTERVAL) or t + ceil(AvgTime) + ttl (ALONE), ttl being
         lock_ttl_batch at now = t.  granted + skipped == profile().  Locks
-        held at t0 are not known (cold start)."""
+        held at t0 are not known (cold start).  what="running": the commands
+        in flight at each bucket edge e_b = t0 + (b+1)*width counting only the
+        granted fires g (e_b - d < g <= e_b, d = ceil(max(AvgTime, 0)) for both
+        kinds); rows of COMMON units and of non-contending rules are
+        inflight()'s, and an ALONE unit's cells sum to at most 1."""
         sp = self._specs(specs)
         k, a, u, c, ttl, w = self._lock_args(sp.n, kind, avg_time_ms, unit, contends, lock_ttl, what)
         check(lib().cg_lock_profile_device(self._h, sp._h, self._loc(loc).handle, int(t0), int(width), int(n_buckets),
@@ -1061,10 +1071,20 @@ class Engine:
         check(lib().cg_last_kernel_times(self._h, buf, 22))
         return [buf[19], buf[21]]
 
+    def running_kernel_times(self):
+        """ms of the prefix sum along the rewritten rows of the last running
+        profile, admit*(what="running") or lock_runs*(what="running")
+        (cg_last_kernel_times [22], k_rows_prefix); 0 after any other kind."""
+        buf = (C.c_float * 23)()
+        check(lib().cg_last_kernel_times(self._h, buf, 23))
+        return buf[22]
+
     def profile_kind(self):
         """What the readable profile holds: _lib.PROFILE_STARTS,
-        PROFILE_INFLIGHT, PROFILE_ADMITTED, PROFILE_DROPPED, PROFILE_LOCK_GRANTED
-        or PROFILE_LOCK_SKIPPED (cg_profile_kind)."""
+        PROFILE_INFLIGHT, PROFILE_ADMITTED, PROFILE_DROPPED, PROFILE_LOCK_GRANTED,
+        PROFILE_LOCK_SKIPPED, PROFILE_RUNNING (commands in flight after
+        Job.limit(), admit*(what="running")) or PROFILE_LOCK_RUNNING (after the
+        job lock, lock_runs*(what="running")) (cg_profile_kind)."""
         k = C.c_int()
         check(lib().cg_profile_kind(self._h, C.byref(k)))
         return k.value

@@ -27,8 +27,8 @@ import numpy as np
 
 from . import _lib
 from ._lib import check, lib
-from .model import (_Interned, admission_units, drops_of, durations_of, job_lock_runs_of, lock_skips_of,
-                    peak_rules_of)
+from .model import (_Interned, admission_units, drops_of, durations_of, job_lock_running_of, job_lock_runs_of,
+                    lock_skips_of, peak_rules_of)
 
 
 def _docs_array(docs):
@@ -116,6 +116,22 @@ class EtcdJobSet(_Interned):
         return drops_of(self, eng, specs, rin, t0, width, n_buckets, dur, self.rule_parallels(), unit, loc, mode,
                         what), [self.job_id(j).decode() for j in split]
 
+    def node_running(self, t0, width, n_buckets, loc=None, mode=_lib.EXCLUDE_NONE, engine=None):
+        """Commands running per node at each bucket edge counting only the fires
+        Job.limit() lets start: ({node ID: int64 [n_buckets]}, the IDs of the
+        jobs that were split), as JobSet.node_running."""
+        return self.node_drops(t0, width, n_buckets, loc, mode, engine, what="running")
+
+    def job_lock_running(self, t0, width, n_buckets, loc=None, mode=_lib.EXCLUDE_NONE, lock_ttl=300, engine=None):
+        """{job ID: int64 [n_buckets]} for the exclusive jobs, cluster-wide: the
+        job's commands running at each bucket edge counting only the fires that
+        find its lock free, as JobSet.job_lock_running."""
+        from .engine import default_engine
+        eng = engine or default_engine()
+        kind, avg = self.rule_kinds()
+        return job_lock_running_of(eng, eng.upload_c(self.schedules_c(), self.n_rules), self.rules_in(), t0, width,
+                                   n_buckets, kind, avg, loc, mode, lock_ttl, lambda j: self.job_id(j).decode())
+
     def rule_kinds(self):
         """(kind int32 [n_rules], avg_time_ms int64 [n_rules]), as JobSet.rule_kinds."""
         kind, avg, _ = self.job_meta()
@@ -159,16 +175,23 @@ class EtcdJobSet(_Interned):
         return {self.node_id(n): counts[n] for n in range(rin.n_nodes)}, missing
 
     def node_peak_rules(self, t0, width, n_buckets, k=10, inflight=False, loc=None, mode=_lib.EXCLUDE_NONE,
-                        engine=None):
+                        engine=None, running=False):
         """Which rules make up each node's peak: {node ID: (peak, bucket,
         [(job ID, rule ID, count), ...])}, with inflight=True (that, rules
-        without an estimate), as JobSet.node_peak_rules."""
+        without an estimate), with running=True (that, the IDs of the jobs that
+        were split), as JobSet.node_peak_rules."""
         from .engine import default_engine
         eng = engine or default_engine()
-        dur, missing = self.rule_durations() if inflight else (None, 0)
-        res = peak_rules_of(self, eng, eng.upload_c(self.schedules_c(), self.n_rules), self.rules_in(), t0, width,
+        if inflight and running:
+            raise ValueError("inflight and running are two profiles: choose one")
+        rin = self.rules_in()
+        dur, missing = self.rule_durations() if inflight or running else (None, 0)
+        unit, split = admission_units(rin, mode) if running else (None, [])
+        res = peak_rules_of(self, eng, eng.upload_c(self.schedules_c(), self.n_rules), rin, t0, width,
                             n_buckets, k, dur, loc, mode, lambda j: self.job_id(j).decode(),
-                            lambda r: self.rule_id(r).decode())
+                            lambda r: self.rule_id(r).decode(), (self.rule_parallels(), unit) if running else None)
+        if running:
+            return res, [self.job_id(j).decode() for j in split]
         return (res, missing) if inflight else res
 
 

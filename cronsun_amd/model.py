@@ -250,6 +250,31 @@ class JobSet(_Interned):
         return drops_of(self, eng, specs, rin, t0, width, n_buckets, dur, self.rule_parallels(), unit, loc, mode,
                         what), [self.jobs[j].ID for j in split]
 
+    def node_running(self, t0, width, n_buckets, loc=None, mode=_lib.EXCLUDE_NONE, engine=None):
+        """Commands running per node at each bucket edge t0 + (b+1)*width,
+        counting only the fires Job.limit() lets start
+        (Engine.admit_per_node, what="running"): ({node ID: int64
+        [n_buckets]}, the IDs of the jobs that were split).  node_inflight
+        less the fires node_drops counts: a job that overruns its period
+        shows as Parallels running copies, not as an ever-growing count.
+        Durations, limits, units and what is not reproduced are node_drops';
+        the job lock is not applied here (job_lock_running)."""
+        return self.node_drops(t0, width, n_buckets, loc, mode, engine, what="running")
+
+    def job_lock_running(self, t0, width, n_buckets, loc=None, mode=_lib.EXCLUDE_NONE, lock_ttl=300, engine=None):
+        """{job ID: int64 [n_buckets]} for the KindAlone / KindInterval jobs,
+        cluster-wide: the job's commands running at each bucket edge t0 +
+        (b+1)*width, counting only the fires that find the job's lock free
+        (Engine.lock_runs, what="running") -- each cluster-wide run once,
+        however many nodes the job is scheduled on.  Each run takes the job's
+        AvgTime; Parallels of an interval job is not applied.  Taken as
+        job_lock_runs, with its limits."""
+        from .engine import default_engine
+        eng = engine or default_engine()
+        kind, avg = self.rule_kinds()
+        return job_lock_running_of(eng, eng.upload(self.schedules()), self.rules_in(), t0, width, n_buckets, kind,
+                                   avg, loc, mode, lock_ttl, lambda j: self.jobs[j].ID)
+
     def rule_kinds(self):
         """(kind int32 [n_rules], avg_time_ms int64 [n_rules]): each rule's
         job's Kind and AvgTime as stored (Engine.lock_runs' arguments)."""
@@ -310,7 +335,7 @@ class JobSet(_Interned):
         return {self.node_id(n): counts[n] for n in range(rin.n_nodes)}, missing
 
     def node_peak_rules(self, t0, width, n_buckets, k=10, inflight=False, loc=None, mode=_lib.EXCLUDE_NONE,
-                        engine=None):
+                        engine=None, running=False):
         """Which rules make up each node's peak: {node ID: (peak, bucket,
         [(job ID, rule ID, count), ...])} -- the largest cell of the node's
         row in the profile of node_profile (inflight=True: of node_inflight),
@@ -319,12 +344,21 @@ class JobSet(_Interned):
         and cut to k (at most _lib.TOP_RULES_MAX).  A node that runs nothing
         gives (0, 0, []).  With inflight=True the durations come from
         rule_durations() and the result is (that dict, rules without an
-        estimate), as node_inflight."""
+        estimate), as node_inflight.  With running=True the profile is
+        node_running's (in flight after Job.limit()) and the result is (that
+        dict, the IDs of the jobs that were split)."""
         from .engine import default_engine
         eng = engine or default_engine()
-        dur, missing = self.rule_durations() if inflight else (None, 0)
-        res = peak_rules_of(self, eng, eng.upload(self.schedules()), self.rules_in(), t0, width, n_buckets, k, dur,
-                            loc, mode, lambda j: self.jobs[j].ID, lambda r: self.rules[r].ID)
+        if inflight and running:
+            raise ValueError("inflight and running are two profiles: choose one")
+        rin = self.rules_in()
+        dur, missing = self.rule_durations() if inflight or running else (None, 0)
+        unit, split = admission_units(rin, mode) if running else (None, [])
+        res = peak_rules_of(self, eng, eng.upload(self.schedules()), rin, t0, width, n_buckets, k, dur,
+                            loc, mode, lambda j: self.jobs[j].ID, lambda r: self.rules[r].ID,
+                            (self.rule_parallels(), unit) if running else None)
+        if running:
+            return res, [self.jobs[j].ID for j in split]
         return (res, missing) if inflight else res
 
     def schedules(self):
@@ -428,14 +462,29 @@ def job_lock_runs_of(eng, specs, rin, t0, width, n_buckets, kind, avg, loc, mode
     return out
 
 
-def peak_rules_of(js, eng, specs, rin, t0, width, n_buckets, k, dur, loc, mode, job_id, rule_id):
+def job_lock_running_of(eng, specs, rin, t0, width, n_buckets, kind, avg, loc, mode, lock_ttl, job_id):
+    """job_lock_running of a job set: per exclusive job the sum of its rules'
+    LOCK_RUNNING rows."""
+    try:
+        unit, contends = lock_units(rin), eng.rule_contends(rin, mode)
+        rows = eng.lock_runs(specs, loc, t0, width, n_buckets, kind, avg, unit, contends, lock_ttl, "running")[0]
+    finally:
+        specs.free()
+    return {job_id(j): rows[unit == j].sum(axis=0, dtype=np.int64)
+            for j in np.unique(unit[np.asarray(kind) != KindCommon]).tolist()}
+
+
+def peak_rules_of(js, eng, specs, rin, t0, width, n_buckets, k, dur, loc, mode, job_id, rule_id, limits=None):
     """node_peak_rules of a job set: the per-node profile (in flight when dur
-    is given), each node's peak, and its top list at the peak bucket mapped
-    back to (job ID, rule ID, count)."""
+    is given; running, i.e. in flight after Job.limit(), when limits =
+    (parallels, unit) is given too), each node's peak, and its top list at the
+    peak bucket mapped back to (job ID, rule ID, count)."""
     drules = eng.upload_rules(rin)
     try:
         if dur is None:
             eng.profile_per_node(specs, loc, t0, width, n_buckets, drules, mode)
+        elif limits is not None:
+            eng.admit_per_node(specs, loc, t0, width, n_buckets, dur, limits[0], limits[1], drules, mode, "running")
         else:
             eng.inflight_per_node(specs, loc, t0, width, n_buckets, dur, drules, mode)
         peak, _ = eng.profile_node_peaks()

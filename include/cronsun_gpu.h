@@ -345,8 +345,10 @@ int cg_result_copy_offsets(cg_ctx* ctx, int64_t* host_offsets /* [R+1] */);
  * cg_dispatcher_fanout; of the last profile call (starts or in flight): [14] rule matrix, [15]
  * walked runs, [16] totals, [17] join + transpose (when rebuilt), [18] node
  * matrix; of the last admission or lock profile: [19] the pass that zeroes the
- * rewritten rows, [20] the admission unit walk, [21] the lock unit walk (22
- * entries in all).  n = entries written. */
+ * rewritten rows, [20] the admission unit walk, [21] the lock unit walk; of
+ * the last running profile (CG_PROFILE_RUNNING / CG_PROFILE_LOCK_RUNNING): [22]
+ * the prefix sum along the rewritten rows (23 entries in all).  n = entries
+ * written. */
 int cg_last_kernel_times(cg_ctx* ctx, float* ms, int n);
 /* Expansion phase timing: 2 (default) = a HIP event between every phase;
  * 1 = events around k_write_cf only ([3]; [0..2], [4], [5] read -1).  Events
@@ -729,8 +731,26 @@ int cg_inflight_per_node_device(cg_ctx* ctx, const cg_specs* specs, const cg_zon
  * shares the 64 KiB of LDS with the staged plan: a horizon whose plan exceeds
  * 46 KiB -- decades -- with a unit that can drop is CG_ERANGE too.)
  *
- * `what` is CG_PROFILE_ADMITTED or CG_PROFILE_DROPPED and selects the rule
- * matrix; cg_profile_kind reports it.  The call is a profile call: it replaces
+ * `what` is CG_PROFILE_ADMITTED, CG_PROFILE_DROPPED or CG_PROFILE_RUNNING and
+ * selects the rule matrix; cg_profile_kind reports it.
+ *
+ * CG_PROFILE_RUNNING is the in-flight profile counting only the fires that
+ * start: with the bucket edges e_b = t0 + (b+1)*w,
+ *   running[r][b] = #{ admitted fires a of rule r : e_b - d_r < a <= e_b }
+ * "Admitted" is the literal process above and d_r the same clamped whole
+ * seconds, so a*1000 + dur_ms > e_b*1000: started and not yet finished at the
+ * edge.  Rows of units that never drop are the rows of cg_inflight_device with
+ * the same dur_ms.  It follows that running <= in flight cell by cell; that a
+ * unit with d == w has its ADMITTED rows, one with d == m*w the sliding sum of
+ * m ADMITTED buckets, one with d >= B*w their prefix sums; and that the cells
+ * of a unit that can drop sum to at most P at every edge.  What is not
+ * reproduced is the list below, unchanged: cold start (the rows ramp up),
+ * same-second order, the locks (limit() and lock() are not composed: this kind
+ * ignores the lock, CG_PROFILE_LOCK_RUNNING ignores Parallels of INTERVAL
+ * jobs), Retry / Interval, actual run times.  Arguments and checks are those of
+ * the other two kinds.
+ *
+ * The call is a profile call: it replaces
  * the readable profile, and bucket totals, the node matrix,
  * cg_profile_result_device, cg_profile_copy_*, cg_profile_node_peaks and
  * cg_profile_top_rules_* serve it as they serve the other kinds.  The node
@@ -744,9 +764,12 @@ int cg_inflight_per_node_device(cg_ctx* ctx, const cg_specs* specs, const cg_zon
  * the CG_ERANGE above are raised with the other argument checks before any
  * device work; the previous profile stays readable.
  * cg_last_kernel_times [14..18] as the start profile's, [19] the pass that
- * zeroes the rewritten rows, [20] the unit walk (k_admit_units). */
+ * zeroes the rewritten rows, [20] the unit walk (k_admit_units); of a RUNNING
+ * call [14], [15] are the in-flight profile's kernels and [22] the prefix sum
+ * along the rewritten rows (k_rows_prefix), 0 otherwise. */
 #define CG_PROFILE_ADMITTED 2
 #define CG_PROFILE_DROPPED 3
+#define CG_PROFILE_RUNNING 7
 #define CG_ADMIT_MAX_PARALLELS 16
 int cg_admit_device(cg_ctx* ctx, const cg_specs* specs, const cg_zone* z, int64_t t0, int64_t width,
                     int32_t n_buckets, const int64_t* dur_ms /* host, [R] */,
@@ -815,9 +838,24 @@ int cg_admit_per_node_device(cg_ctx* ctx, const cg_specs* specs, const cg_zone* 
  * Rows of COMMON units and of non-contending rules: granted is the start row,
  * skipped is zero.
  *
- * `what` is CG_PROFILE_LOCK_GRANTED or CG_PROFILE_LOCK_SKIPPED and selects the
- * rule matrix; cg_profile_kind reports it.  The call is a profile call: it
- * replaces the readable profile, and bucket totals, the node matrix,
+ * `what` is CG_PROFILE_LOCK_GRANTED, CG_PROFILE_LOCK_SKIPPED or
+ * CG_PROFILE_LOCK_RUNNING and selects the rule matrix; cg_profile_kind reports
+ * it.
+ *
+ * CG_PROFILE_LOCK_RUNNING is the in-flight profile counting only the fires that
+ * are granted: with the bucket edges e_b = t0 + (b+1)*w,
+ *   running[r][b] = #{ granted fires g of rule r : e_b - d_r < g <= e_b }
+ * for both kinds: an INTERVAL command runs d_r seconds whatever its lease does.
+ * "Granted" is the literal process above, step 4's CG_ERANGE included.  Rows of
+ * COMMON units and of non-contending rules are the rows of cg_inflight_device
+ * with that d_r (avg <= 0: a zero row).  running <= in flight cell by cell; a
+ * unit with d == w has its GRANTED rows, d == m*w their sliding sum over m
+ * buckets, d >= B*w their prefix sums; the cells of an ALONE unit sum to at
+ * most 1 at every edge (free_at = g + d + ttl, ttl >= 2).  The node matrix is
+ * an upper bound as GRANTED's is (which node wins a free lock is not
+ * decidable); the totals count each cluster-wide run once.
+ *
+ * The call is a profile call: it replaces the readable profile, and bucket totals, the node matrix,
  * cg_profile_result_device, cg_profile_copy_*, cg_profile_node_peaks and
  * cg_profile_top_rules_* serve it unchanged.
  *   - The SKIPPED node row is exact: the fires of node n's Cmds at which the
@@ -842,14 +880,18 @@ int cg_admit_per_node_device(cg_ctx* ctx, const cg_specs* specs, const cg_zone* 
  * All argument checks run before any device work, and the previous profile
  * stays readable: NULL kind or avg_time_ms with R > 0, a kind that is none of
  * the three, a decreasing unit, a mixed unit (each CG_EINVAL naming the first
- * such rule), lock_ttl < 2, `what` not 4 or 5.  The zone table of the call
+ * such rule), lock_ttl < 2, `what` not 4, 5 or 8.  The zone table of the call
  * reaches from the zero time to 12 years past t1, as cg_lock_ttl_batch's; if
  * it, the plan and the walked runs' remembered positions (10 KiB) do not fit
  * the 64 KiB of LDS the call fails with CG_ERANGE.
  * cg_last_kernel_times [14..18] as the start profile's, [19] the pass that
- * zeroes the rewritten rows, [21] the unit walk (k_lock_units); [20] is 0. */
+ * zeroes the rewritten rows, [21] the unit walk (k_lock_units); [20] is 0.  Of
+ * a LOCK_RUNNING call [14], [15] are the in-flight profile's kernels and [22]
+ * the prefix sum along the rewritten rows (k_rows_prefix), 0 otherwise. */
 #define CG_PROFILE_LOCK_GRANTED 4
 #define CG_PROFILE_LOCK_SKIPPED 5
+/* (6 is not assigned) */
+#define CG_PROFILE_LOCK_RUNNING 8
 int cg_lock_profile_device(cg_ctx* ctx, const cg_specs* specs, const cg_zone* z, int64_t t0, int64_t width,
                            int32_t n_buckets, const int32_t* kind /* host, [R] */,
                            const int64_t* avg_time_ms /* host, [R] */,
@@ -862,8 +904,9 @@ int cg_lock_profile_per_node_device(cg_ctx* ctx, const cg_specs* specs, const cg
                                     const uint8_t* contends /* host, [R]; may be NULL */, int64_t lock_ttl,
                                     int what, const cg_rules* rules, int mode);
 /* *kind = CG_PROFILE_STARTS, CG_PROFILE_INFLIGHT, CG_PROFILE_ADMITTED,
- * CG_PROFILE_DROPPED, CG_PROFILE_LOCK_GRANTED or CG_PROFILE_LOCK_SKIPPED: what
- * the readable profile holds.  CG_EINVAL when no profile is readable. */
+ * CG_PROFILE_DROPPED, CG_PROFILE_LOCK_GRANTED, CG_PROFILE_LOCK_SKIPPED,
+ * CG_PROFILE_RUNNING or CG_PROFILE_LOCK_RUNNING: what the readable profile
+ * holds.  CG_EINVAL when no profile is readable. */
 int cg_profile_kind(cg_ctx* ctx, int* kind);
 /* Per node row [first_node, first_node + count) of the last profile's node
  * matrix (of either kind): its largest cell and the first bucket attaining it;

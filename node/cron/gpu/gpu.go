@@ -492,6 +492,16 @@ const (
 	// the two kinds of LockProfile / LockProfilePerNode
 	ProfileLockGranted = C.CG_PROFILE_LOCK_GRANTED
 	ProfileLockSkipped = C.CG_PROFILE_LOCK_SKIPPED
+	// ProfileRunning, a `what` of Admit / AdmitPerNode: the commands in flight
+	// at each bucket edge counting only the fires Job.limit() lets start
+	// (the in-flight profile less the dropped fires; a unit's cells sum to
+	// at most its Parallels).
+	ProfileRunning = C.CG_PROFILE_RUNNING
+	// ProfileLockRunning, a `what` of LockProfile / LockProfilePerNode: the
+	// commands in flight counting only the fires that find the job's lock
+	// free; each runs ceil(AvgTime) seconds whatever its lease does.  The
+	// node matrix is an upper bound, as ProfileLockGranted's.
+	ProfileLockRunning = C.CG_PROFILE_LOCK_RUNNING
 )
 
 // durations checks one duration per rule and returns the pointer C reads
@@ -785,8 +795,8 @@ func (e *Engine) LockProfilePerNode(sp *Specs, z *Zone, t0 time.Time, width time
 }
 
 // ProfileKind reports what the readable profile holds: ProfileStarts,
-// ProfileInFlight, ProfileAdmitted, ProfileDropped, ProfileLockGranted or
-// ProfileLockSkipped.
+// ProfileInFlight, ProfileAdmitted, ProfileDropped, ProfileLockGranted,
+// ProfileLockSkipped, ProfileRunning or ProfileLockRunning.
 func (e *Engine) ProfileKind() (int, error) {
 	defer runtime.KeepAlive(e)
 	var kind C.int
