@@ -178,6 +178,7 @@ def _declare(L):
         "cg_expand_per_node_device": ([vp, vp, vp, i64, i64, P(cg_rules_in), C.c_int, P(i64), P(i64)], C.c_int),
         "cg_node_result_device": ([vp, P(vp), P(vp), P(vp), P(i64)], C.c_int),
         "cg_node_result_copy": ([vp, vp, vp, vp, i64], C.c_int),
+        "cg_node_result_bands": ([vp, P(i32), P(i32)], C.c_int),
         "cg_node_counts_to_device": ([vp, vp], C.c_int),
         "cg_node_checksum_enqueue": ([vp, vp, C.c_int32, vp], C.c_int),
         "cg_node_csr_place": ([vp, C.c_int32, vp, vp, vp, C.c_int32, vp, vp, vp], C.c_int),

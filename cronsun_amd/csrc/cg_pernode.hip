@@ -1057,6 +1057,15 @@ int cg_node_result_device(cg_ctx* c, const int64_t** d_node_off, const int64_t**
   return CG_OK;
 }
 
+int cg_node_result_bands(cg_ctx* c, int32_t* rules_per_band, int32_t* n_bands) {
+  if (!c) return cg_fail(CG_EINVAL, "cg_node_result_bands: null");
+  std::lock_guard<std::mutex> g(c->mu);
+  if (c->pn_K == 0) return cg_fail(CG_EINVAL, "cg_node_result_bands: no synchronous per-node call yet");
+  if (rules_per_band) *rules_per_band = c->pn_B;
+  if (n_bands) *n_bands = c->pn_K;
+  return CG_OK;
+}
+
 int cg_node_result_copy(cg_ctx* c, int64_t* node_off, int64_t* time, int32_t* rule, int64_t cap) {
   if (!c) return cg_fail(CG_EINVAL, "cg_node_result_copy: null");
   std::lock_guard<std::mutex> g(c->mu);

@@ -677,6 +677,14 @@ class Engine:
                                         rule.ctypes.data, n_events))
         return node_off, time[:n_events], rule[:n_events]
 
+    def node_bands(self):
+        """(B, K) of the last successful synchronous per-node call, which
+        pipelined windows reuse (cg_node_result_bands): every node's list is
+        written in K = ceil(R / B) segments of B consecutive rules."""
+        b, k = C.c_int32(), C.c_int32()
+        check(lib().cg_node_result_bands(self._h, C.byref(b), C.byref(k)))
+        return b.value, k.value
+
     def node_checksum_enqueue(self, d_nodes, k, d_out):
         """cg_node_checksum_enqueue: checksums of k nodes' lists of the last
         enqueued window (device pointers: int32 nodes [k], uint64 out [2k])."""

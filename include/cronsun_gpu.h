@@ -472,6 +472,12 @@ int cg_expand_per_node_device(cg_ctx* ctx, const cg_specs* specs, const cg_zone*
 /* device pointers of the last per-node result */
 int cg_node_result_device(cg_ctx* ctx, const int64_t** d_node_off, const int64_t** d_time,
                           const int32_t** d_rule, int64_t* n_events);
+/* The rule bands of the last successful synchronous per-node call
+ * (cg_expand_per_node*), which pipelined windows reuse: every node's list is
+ * written in K = ceil(n_rules / B) segments of B consecutive rules (B >=
+ * 32768 unless a band would hold more than 2^30 fires).  Read-only, no device
+ * work; either pointer may be NULL.  CG_EINVAL before the first such call. */
+int cg_node_result_bands(cg_ctx* ctx, int32_t* rules_per_band, int32_t* n_bands);
 /* Reorder every node's list of the last per-node result by (time, rule), in
  * device memory: the order the node's scheduler keeps its entries in
  * (Cron.run's sort.Sort(byTime), node/cron/cron.go:64-79,220; equal times in

@@ -400,9 +400,10 @@ def test_per_node_progressions_vs_oracle(eng, zone, t0):
     progression records: t0 + x + p * stride) against the oracle: every-second,
     @every, hourly, daily (a 23/25-h step across the NY DST change breaks the
     progression), weekly, never-firing and non-progression rules, over 3 days
-    and 3 rule bands, with every-second rules early in a node's band so the
-    positions of later daily rules overflow the record's 32-bit x (those fall
-    back to gathers)."""
+    in one rule band (2600 rules; bands hold at least 32768: overflow3 of
+    tests/test_gpu_pernode_bands.py runs 3 bands), with every-second rules
+    early in a node's list so the positions of later daily rules overflow the
+    record's 32-bit x (those fall back to gathers)."""
     R, N = 2600, 6
     specs = [PROGRESSION_MIX[1 + i % (len(PROGRESSION_MIX) - 1)] for i in range(R)]
     for i in (0, 1, 1030, 2100):  # a few every-second rules (259 200 fires each), early in bands
@@ -533,9 +534,10 @@ def test_per_node_async_windows(zone, order):
 
 
 def test_per_node_bands_past_2_30_fires():
-    """A window whose 1024-rule bands hold more than 2^30 fires (1024
-    every-second rules over 13 days: 1.15 G fires): the per-node path narrows
-    its bands instead of refusing, and sampled nodes' lists are bit-exact
+    """A window whose first 1024 rules hold more than 2^30 fires (1024
+    every-second rules over 13 days: 1.15 G fires): the per-node path halves
+    its one band of 1100 rules until each holds fewer (K >= 3 bands) instead
+    of refusing, and sampled nodes' lists are bit-exact
     against the oracle (job.go:591-614 composed with spec.go:55-145 over the
     whole window)."""
     from cronsun_amd.engine import Engine
@@ -551,6 +553,7 @@ def test_per_node_bands_past_2_30_fires():
     t1 = t0 + 13 * DAY
     En, nnz = e2.expand_per_node_rules_device(sp, cron.UTC(), t0, t1, dr, _lib.EXCLUDE_NONE)
     assert En > 2 * (1 << 30)
+    assert e2.node_bands()[1] >= 3
     from cronsun_amd._lib import check, lib
     off = np.empty(N + 1, np.int64)
     check(lib().cg_node_result_copy(e2._h, off.ctypes.data, None, None, 0))
