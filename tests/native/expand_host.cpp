@@ -32,6 +32,34 @@ static const char* long_specials[] = {"@yearly", "@monthly", "@weekly", "@daily"
                                       "59 59 23 28,29 Feb ?", "0 0 12 29 Feb Mon", "0 30 2 * * *",
                                       "0 30 1 * * Sun", "0 0 0 31 * ?", "0 0 0 30 Feb ?"};
 
+// masks mode: rule i has 1 + i % 60 second bits, 1 + 7i % 60 minute bits and
+// 1 + 5i % 24 hour bits, each a uniform random subset written as a comma list
+// (120 rules hold every value of each radix and 120 distinct triples); the
+// day fields cycle through "* * *", a dom list, a dow list and both, one rule
+// in five has a month list.  sparse: at most 3 second bits (long horizons).
+static std::string subset(std::mt19937_64& rng, int n, int lo, int hi) {
+  std::vector<int> v;
+  for (int x = lo; x <= hi; x++) v.push_back(x);
+  for (int k = 0; k < n; k++) std::swap(v[k], v[k + rng() % (v.size() - k)]);
+  std::sort(v.begin(), v.begin() + n);
+  std::string out;
+  for (int k = 0; k < n; k++) out += (k ? "," : "") + std::to_string(v[k]);
+  return out;
+}
+static std::string mask_spec(std::mt19937_64& rng, int i, bool sparse) {
+  const int nS = 1 + i % 60, nM = 1 + 7 * i % 60, nH = 1 + 5 * i % 24;
+  std::string spec = subset(rng, sparse ? 1 + (nS - 1) % 3 : nS, 0, 59) + " " + subset(rng, nM, 0, 59) + " " +
+                     subset(rng, nH, 0, 23) + " ";
+  const std::string dom = subset(rng, 25 + int(rng() % 6), 1, 31), dow = subset(rng, 5 + int(rng() % 2), 0, 6);
+  const std::string month = i % 5 == 0 ? subset(rng, 9 + int(rng() % 3), 1, 12) : "*";
+  switch (i % 4) {
+    case 0: return spec + "* " + month + " *";
+    case 1: return spec + dom + " " + month + " *";
+    case 2: return spec + "? " + month + " " + dow;
+    default: return spec + dom + " " + month + " " + dow;
+  }
+}
+
 int main(int argc, char** argv) {
   const char* zone = argc > 1 ? argv[1] : "UTC";
   int nspec = argc > 2 ? atoi(argv[2]) : 400;
@@ -39,13 +67,28 @@ int main(int argc, char** argv) {
   // near mode: T0 at many offsets around transitions of 2011-2027 (just before,
   // on, inside the overlap, hours and days after), 30-hour horizons
   const bool near_mode = argc > 4 && std::string(argv[4]) == "near";
+  // masks mode: the stratified random masks above over one day and the 24 h
+  // around each transition, and their sparse form over 40 days
+  const bool masks_mode = argc > 4 && std::string(argv[4]) == "masks";
   ZoneRules zr;
   or_loc* ol = nullptr;
   load_zone(zone, &zr, &ol);
   std::mt19937_64 rng(argc > 3 ? strtoull(argv[3], nullptr, 10) : 777);
-  std::vector<or_sched> scheds;
-  std::vector<std::string> names;
+  std::vector<or_sched> scheds, sparse_scheds;
+  std::vector<std::string> names, sparse_names;
   size_t nspecial = 0;
+  for (int i = 0; masks_mode && i < 2 * nspec; i++) {
+    const bool sparse = i >= nspec;
+    const std::string spec = mask_spec(rng, i % nspec, sparse);
+    or_sched s;
+    char err[256];
+    if (or_parse(OR_OPT_DEFAULT, spec.c_str(), spec.size(), &s, err, sizeof err)) {
+      printf("masks: [%s] does not parse: %s\n", spec.c_str(), err);
+      return 2;
+    }
+    (sparse ? sparse_scheds : scheds).push_back(s);
+    (sparse ? sparse_names : names).push_back(spec);
+  }
   while ((int)scheds.size() < nspec) {
     std::string spec;
     if (long_mode && nspecial < sizeof long_specials / sizeof long_specials[0])
@@ -101,11 +144,27 @@ int main(int argc, char** argv) {
       for (int k = 1; k < 40; k += (i % 3) + 1) hz.push_back({nt.when[i] + k * 86400 + 3 * k * 877, nt.when[i] + k * 86400 + 3 * k * 877 + 86400});
     }
   }
+  std::vector<char> hz_sparse(hz.size(), 0);
+  if (masks_mode) {
+    std::vector<std::pair<int64_t, int64_t>> keep = {{1767571200 + 1234, 1767571200 + 86400}};
+    for (auto h : hz)  // the first two transitions: one each way
+      if (h.second - h.first == 43217 + 43200 && keep.size() < 3) keep.push_back(h);
+    keep.push_back({1767571200 - 77, 1767571200 + 40 * 86400});
+    hz = keep;
+    hz_sparse.assign(hz.size(), 0);
+    hz_sparse.back() = 1;
+  }
   if (long_mode)  // three years from 2026; 2095-06-01 .. 2106-06-01 (Feb 29 gap over 2100)
     hz = {{1767571200 - 77, 1767571200 + 1096 * 86400}, {3957984000, 3957984000 + 4018 * 86400}};
   int bad = 0;
   long long total = 0;
-  for (auto [t0, t1] : hz) {
+  const std::vector<or_sched>& scheds_all = scheds;
+  const std::vector<std::string>& names_all = names;
+  for (size_t hi = 0; hi < hz.size(); hi++) {
+    const auto [t0, t1] = hz[hi];
+    const bool use_sparse = masks_mode && hz_sparse[hi];
+    const std::vector<or_sched>& scheds = use_sparse ? sparse_scheds : scheds_all;
+    const std::vector<std::string>& names = use_sparse ? sparse_names : names_all;
     Plan plan = build_plan(zr, t0, t1);
     ZoneView zv{plan.table.when.data(), plan.table.off.data(), int32_t(plan.table.when.size())};
     int G = int(plan.segs.size());
@@ -150,10 +209,13 @@ int main(int argc, char** argv) {
           for (int k = 0; k < cnt[s]; k++) { t = next_exact(d, zv, t, t1); got.push_back(t); }
         }
       }
-      int64_t n = or_expand(&scheds[r], t0, t1, ol, nullptr, 0);
+      // one pass of the oracle's loop where it agrees on the count (room for one more fire)
+      std::vector<int64_t> exp(got.size() + 1);
+      int64_t n = or_expand(&scheds[r], t0, t1, ol, exp.data(), int64_t(exp.size()));
       if (n < 0) { if (ok) { if (bad++ < 10) printf("NOPROGRESS mismatch %s (%lld,%lld] got %zu fires, G=%d\n", names[r].c_str(), (long long)t0, (long long)t1, got.size(), G); } continue; }
-      std::vector<int64_t> exp(n);
-      or_expand(&scheds[r], t0, t1, ol, exp.data(), n);
+      const bool fits = size_t(n) <= exp.size();
+      exp.resize(n);
+      if (!fits) or_expand(&scheds[r], t0, t1, ol, exp.data(), n);
       total += n;
       if (got != exp && bad++ < 10) {
         size_t i = 0;

@@ -63,6 +63,21 @@ def test_host_algorithm_near_transitions(expand_host, zone):
     assert " 0 mismatches" in out.stdout
 
 
+@pytest.mark.parametrize("zone", ["UTC", "America/New_York", "Australia/Lord_Howe", "America/Havana"])
+def test_host_algorithm_random_masks(expand_host, zone):
+    """Random second, minute and hour masks of every size (every popcount of
+    each level: 120 rules with 120 distinct triples in UTC, 60 rules in the
+    zones with transitions, where the oracle's walk is several times slower;
+    random dom, month and dow lists) over one day from a midnight + 1234 s and
+    the 24 h around the zone's first two transitions of 2025, and with at most
+    three second bits over 40 days."""
+    out = subprocess.run([expand_host, zone, "120" if zone == "UTC" else "60", "23", "masks"], cwd=ROOT,
+                         capture_output=True, text=True, timeout=300)
+    assert out.returncode == 0, out.stdout[-2000:] + out.stderr[-2000:]
+    assert " 0 mismatches" in out.stdout
+    assert int(out.stdout.split(" mismatches, ")[1].split()[0]) > 1_000_000
+
+
 @pytest.mark.parametrize("zone", ["America/New_York", "Europe/London", "Australia/Sydney", "America/St_Johns",
                                   "Africa/Casablanca"])
 def test_host_algorithm_clean_transitions(expand_host, zone):
