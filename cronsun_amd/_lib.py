@@ -38,6 +38,7 @@ PROFILE_LOCK_GRANTED, PROFILE_LOCK_SKIPPED = 4, 5  # the two kinds of cg_lock_pr
 PROFILE_RUNNING, PROFILE_LOCK_RUNNING = 7, 8  # in flight after Job.limit() (cg_admit_*) / the job lock (cg_lock_profile_*)
 JOB_COMMON, JOB_ALONE, JOB_INTERVAL = 0, 1, 2  # CG_JOB_*: Job.Kind (job.go:30-34)
 ADMIT_MAX_PARALLELS = 16  # CG_ADMIT_MAX_PARALLELS: the largest limit of a unit that can drop
+VERDICT_DROPPED, VERDICT_SKIPPED = 1, 2  # CG_VERDICT_*: bits of a fire's verdict byte (cg_expand_verdicts_device)
 CG_FANOUT_AUTO, CG_FANOUT_FILTER, CG_FANOUT_DUE = 0, 1, 2  # cg_dispatcher_set_fanout_path
 UPCOMING_MAX = 65536  # CG_UPCOMING_MAX: the largest k of cg_dispatcher_upcoming*
 TOP_RULES_MAX = 64  # CG_TOP_RULES_MAX: the largest k of cg_profile_top_rules_*
@@ -81,6 +82,15 @@ class cg_rules_in(C.Structure):
 class cg_node_csr(C.Structure):
     _fields_ = [("node_off", C.c_void_p), ("time", C.c_void_p), ("rule", C.c_void_p),
                 ("cap", C.c_int64), ("n_events", C.c_int64), ("nnz", C.c_int64)]
+
+
+class cg_admit_args(C.Structure):
+    _fields_ = [("dur_ms", C.c_void_p), ("parallels", C.c_void_p), ("unit", C.c_void_p)]
+
+
+class cg_lock_args(C.Structure):
+    _fields_ = [("kind", C.c_void_p), ("avg_time_ms", C.c_void_p), ("unit", C.c_void_p),
+                ("contends", C.c_void_p), ("lock_ttl", C.c_int64)]
 
 
 def _preload_torch_hip():
@@ -209,6 +219,14 @@ def _declare(L):
         "cg_lock_profile_device": ([vp, vp, vp, i64, i64, i32, vp, vp, vp, vp, i64, C.c_int], C.c_int),
         "cg_lock_profile_per_node_device": ([vp, vp, vp, i64, i64, i32, vp, vp, vp, vp, i64, C.c_int, vp, C.c_int],
                                             C.c_int),
+        "cg_expand_verdicts_device": ([vp, vp, vp, i64, i64, P(cg_admit_args), P(cg_lock_args), P(i64)], C.c_int),
+        "cg_verdicts_device": ([vp, P(vp), P(i64)], C.c_int),
+        "cg_verdicts_copy": ([vp, i64, i64, vp], C.c_int),
+        "cg_verdicts_select_device": ([vp, C.c_int, C.c_int, P(i64)], C.c_int),
+        "cg_verdicts_selected_device": ([vp, P(vp), P(vp), P(i64)], C.c_int),
+        "cg_verdicts_selected_copy_offsets": ([vp, vp], C.c_int),
+        "cg_verdicts_selected_copy_times": ([vp, i64, i64, vp], C.c_int),
+        "cg_verdict_times": ([vp, P(C.c_float), C.c_int], C.c_int),
         "cg_profile_kind": ([vp, P(C.c_int)], C.c_int),
         "cg_profile_node_peaks": ([vp, i32, i32, vp, vp], C.c_int),
         "cg_profile_top_rules_nodes": ([vp, i32, vp], C.c_int),

@@ -272,6 +272,25 @@ struct cg_ctx {
   DBuf<char> scan_tmp;
   DBuf<unsigned long long> cksum;  // cg_checksum_device accumulator
   int64_t last_E = 0, last_R = 0;
+  // counts the calls that replace (or clear) the readable rule-major result:
+  // every synchronous count chain, pipelined call and pipelined per-node window
+  uint64_t res_gen = 0;
+
+  // fire verdicts (cg_verdict.hip): one byte per fire of the rule-major result
+  // of generation vd_gen (vd_R rules, vd_E fires), the per-call uploads of the
+  // walks (rule flags = initial verdict bytes, the lock walk's contends, the
+  // compacted units), a device error word {position mismatch, stuck rule}, and
+  // the last selection (sel_off [vd_R + 1], sel_times [vd_nsel])
+  DBuf<uint8_t> vd_verdict, vd_flag, vd_contends;
+  DBuf<char> vd_admit_units, vd_lock_units;
+  DBuf<unsigned long long> vd_err;
+  DBuf<int32_t> vd_sel_cnt;
+  DBuf<int64_t> vd_sel_off, vd_sel_times;
+  uint64_t vd_gen = 0;
+  int64_t vd_R = 0, vd_E = 0, vd_nsel = 0;
+  bool vd_valid = false, vd_sel_valid = false;
+  float vd_ms[6] = {0, 0, 0, 0, 0, 0};  // cg_verdict_times
+  hipEvent_t vdev[8] = {};
 
   // pipelined expansion (cg_async.cpp): the sets used in turn, count + scan
   // on st_cs, writers on st / st_w1; as_last = set of the last async result
@@ -443,6 +462,10 @@ struct cg_ctx {
     pf_admit_units.release(); pf_admit_flag.release(); pf_lock_stuck.release();
     for (hipEvent_t& e : pfev)
       if (e) (void)hipEventDestroy(e), e = nullptr;
+    vd_verdict.release(); vd_flag.release(); vd_contends.release(); vd_admit_units.release();
+    vd_lock_units.release(); vd_err.release(); vd_sel_cnt.release(); vd_sel_off.release(); vd_sel_times.release();
+    for (hipEvent_t& e : vdev)
+      if (e) (void)hipEventDestroy(e), e = nullptr;
   }
 };
 
@@ -501,8 +524,10 @@ void run_set_write_enqueue(const RunSet& rs, const cg_specs* s, int64_t cap, int
                            hipStream_t st, hipEvent_t after_cf = nullptr);
 // the error text of a record whose stuck rule is not ~0
 std::string stuck_msg(unsigned long long rule);
+// (lock_table: the count chain stages the lock profile's zone table, for the
+// walk a verdict call runs behind the writers; the result is the same)
 int expand_device_locked(cg_ctx* c, const cg_specs* s, const cg_zone* z, int64_t t0, int64_t t1,
-                         int64_t* n_events);
+                         int64_t* n_events, bool lock_table = false);
 // finish and check every pending cg_expand_device_async call (cg_async.cpp);
 // their errors are reported by the next cg_expand_wait
 int async_drain(cg_ctx* c);

@@ -168,6 +168,7 @@ int cg_expand_device_async(cg_ctx* c, const cg_specs* s, const cg_zone* z, int64
   check_set(c, a);
   a.done = nullptr;
   c->wr_call++;
+  c->res_gen++;  // this call's writer replaces the readable result
   c->times_last = wi;
   if (wi) c->w1_dirty = true;
   const int64_t R = int64_t(s->n);

@@ -117,6 +117,7 @@ int sync_count_scan(cg_ctx* c, const cg_specs* s, const cg_zone* z, int64_t t0, 
   c->times_last = 0;  // synchronous calls write c->times
   c->last_R = 0;
   c->last_E = 0;
+  c->res_gen++;  // verdicts and selections of the replaced result go stale
   HIPCHK(hipSetDevice(c->device));
   if (t1 - t0 > CG_MAX_HORIZON || t0 < -(int64_t(1) << 45) || t1 > (int64_t(1) << 45))
     return cg_fail(CG_ERANGE, "horizon must satisfy t1 - t0 <= CG_MAX_HORIZON (40 years)");
@@ -134,12 +135,12 @@ int sync_count_scan(cg_ctx* c, const cg_specs* s, const cg_zone* z, int64_t t0, 
 static int stuck_error(unsigned long long stuck) { return cg_fail(CG_ERANGE, stuck_msg(stuck)); }
 
 int expand_device_locked(cg_ctx* c, const cg_specs* s, const cg_zone* z, int64_t t0, int64_t t1,
-                         int64_t* n_events) {
+                         int64_t* n_events, bool lock_table) {
   bool empty = true;
   // steady state: the output buffer exists, so the scan builds the writer's
   // slice map for its capacity (a first or a growing call maps separately)
   const int64_t cap0 = int64_t(c->times.cap);
-  int rc = sync_count_scan(c, s, z, t0, t1, &empty, cap0);
+  int rc = sync_count_scan(c, s, z, t0, t1, &empty, cap0, lock_table);
   if (rc) return rc;
   const int64_t R = int64_t(s->n);
   if (empty) {

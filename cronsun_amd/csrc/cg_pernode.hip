@@ -888,6 +888,7 @@ int cg_expand_per_node_rules_device_async(cg_ctx* c, const cg_specs* s, const cg
   c->times_last = 0;
   c->last_R = 0;
   c->last_E = 0;
+  c->res_gen++;
   const int k = c->pa_next;
   PnAsyncSet& a = c->pns[k];
   // the set was last used kPnSets calls ago: its writer must be done

@@ -61,6 +61,7 @@
 #include "cg_lock.h"
 #include "cg_profile.h"
 #include "cg_stage.h"
+#include "cg_units.h"
 
 using namespace cg;
 
@@ -523,30 +524,7 @@ int ensure_events(cg_ctx* c) {
 // it comes together with adm or lk in a RUNNING call, whose base rows are the
 // in-flight profile's and whose unit walk writes differences that k_rows_prefix
 // sums (pfev[8]: the end of that walk; pfev[2] then follows the prefix).
-// An admission call's checked arguments: the units that can drop, compacted,
-// and per rule whether its unit is one of them.  Host memory that outlives the
-// stream synchronise that ends the call.
-// RUNNING kinds also carry every rule's d (dsec, as an in-flight call's).
-struct AdmitCall {
-  int what = CG_PROFILE_ADMITTED;
-  std::vector<AdmitUnit> units;
-  std::vector<uint8_t> flag;
-  std::vector<int64_t> dsec;
-  bool running() const { return what == CG_PROFILE_RUNNING; }
-  const std::vector<int64_t>* durations() const { return running() ? &dsec : nullptr; }
-};
-// A lock call's: the lock units with a contending rule, compacted, and per
-// rule whether it is a contending rule of a lock unit.
-struct LockCall {
-  int what = CG_PROFILE_LOCK_SKIPPED;
-  int64_t lock_ttl = 0;
-  std::vector<LockUnit> units;
-  std::vector<uint8_t> flag;
-  std::vector<int64_t> dsec;
-  bool running() const { return what == CG_PROFILE_LOCK_RUNNING; }
-  const std::vector<int64_t>* durations() const { return running() ? &dsec : nullptr; }
-};
-
+// adm / lk: an admission or a lock call's checked arguments (cg_units.h).
 int profile_rules_enqueue(cg_ctx* c, const cg_specs* s, const cg_zone* z, int64_t t0, int64_t w, int32_t B,
                           const std::vector<int64_t>* dsec, const AdmitCall* adm = nullptr,
                           const LockCall* lk = nullptr) {
@@ -726,103 +704,6 @@ int profile_call(cg_ctx* c, const cg_specs* s, const cg_zone* z, int64_t t0, int
   HIPCHK(hipStreamSynchronize(c->st));
   profile_rule_times(c);
   c->pf_valid = true;
-  return CG_OK;
-}
-
-// An admission call's per-rule arguments -> the units that can drop.  Units
-// are the maximal runs of equal unit[] (NULL: every rule its own); all checks
-// name the first offending rule.
-int admit_units(const char* what_fn, const cg_specs* s, const int64_t* dur_ms, const int64_t* parallels,
-                const int32_t* unit, int what, int64_t horizon, AdmitCall* out) {
-  const std::string fn(what_fn);
-  if (what != CG_PROFILE_ADMITTED && what != CG_PROFILE_DROPPED && what != CG_PROFILE_RUNNING)
-    return cg_fail(CG_EINVAL, fn + ": what must be CG_PROFILE_ADMITTED, CG_PROFILE_DROPPED or CG_PROFILE_RUNNING");
-  const int64_t R = int64_t(s->n);
-  if (R > 0 && !dur_ms) return cg_fail(CG_EINVAL, fn + ": rule 0: null dur_ms");
-  if (R > 0 && !parallels) return cg_fail(CG_EINVAL, fn + ": rule 0: null parallels");
-  for (int64_t r = 0; r < R; r++) {
-    if (dur_ms[r] < 0) return cg_fail(CG_EINVAL, fn + ": rule " + std::to_string(r) + ": negative duration");
-    if (parallels[r] < 0) return cg_fail(CG_EINVAL, fn + ": rule " + std::to_string(r) + ": negative parallels");
-    if (unit && r > 0 && unit[r] < unit[r - 1])
-      return cg_fail(CG_EINVAL, fn + ": rule " + std::to_string(r) + ": unit decreases");
-  }
-  out->what = what;
-  out->units.clear();
-  out->flag.assign(size_t(R), 0);
-  out->dsec.clear();
-  if (out->running()) {
-    out->dsec.resize(size_t(R));
-    for (int64_t r = 0; r < R; r++) out->dsec[size_t(r)] = inflight_seconds(dur_ms[r], horizon);
-  }
-  for (int64_t r0 = 0; r0 < R;) {
-    int64_t r1 = r0 + 1;
-    if (unit)
-      for (; r1 < R && unit[r1] == unit[r0]; r1++)
-        if (dur_ms[r1] != dur_ms[r0] || parallels[r1] != parallels[r0])
-          return cg_fail(CG_EINVAL, fn + ": rule " + std::to_string(r1) + ": dur_ms / parallels differ inside unit " +
-                                        std::to_string(unit[r0]));
-    const int64_t P = parallels[r0], d = inflight_seconds(dur_ms[r0], horizon), k = r1 - r0;
-    if (!admit_never_drops(P, d, k)) {
-      if (P > CG_ADMIT_MAX_PARALLELS)
-        return cg_fail(CG_ERANGE, fn + ": rule " + std::to_string(r0) + ": parallels " + std::to_string(P) +
-                                      " can drop and exceeds CG_ADMIT_MAX_PARALLELS (16)");
-      if (k > INT32_MAX) return cg_fail(CG_ERANGE, fn + ": rule " + std::to_string(r0) + ": unit too long");
-      out->units.push_back(AdmitUnit{r0, d, int32_t(k), int32_t(P)});
-      for (int64_t r = r0; r < r1; r++) out->flag[size_t(r)] = 1;
-    }
-    r0 = r1;
-  }
-  return CG_OK;
-}
-
-// A lock call's per-rule arguments -> the lock units with a contending rule.
-// Units are the maximal runs of equal unit[] (NULL: every rule its own); all
-// checks name the first offending rule.
-int lock_units(const char* what_fn, const cg_specs* s, const int32_t* kind, const int64_t* avg_ms, const int32_t* unit,
-               const uint8_t* contends, int64_t lock_ttl, int what, int64_t horizon, LockCall* out) {
-  const std::string fn(what_fn);
-  if (what != CG_PROFILE_LOCK_GRANTED && what != CG_PROFILE_LOCK_SKIPPED && what != CG_PROFILE_LOCK_RUNNING)
-    return cg_fail(CG_EINVAL, fn + ": what must be CG_PROFILE_LOCK_GRANTED, CG_PROFILE_LOCK_SKIPPED or "
-                                   "CG_PROFILE_LOCK_RUNNING");
-  if (lock_ttl < 2) return cg_fail(CG_EINVAL, fn + ": lock_ttl must be at least 2 (conf.go:136-138)");
-  const int64_t R = int64_t(s->n);
-  if (R > 0 && !kind) return cg_fail(CG_EINVAL, fn + ": rule 0: null kind");
-  if (R > 0 && !avg_ms) return cg_fail(CG_EINVAL, fn + ": rule 0: null avg_time_ms");
-  for (int64_t r = 0; r < R; r++) {
-    if (kind[r] != CG_JOB_COMMON && kind[r] != CG_JOB_ALONE && kind[r] != CG_JOB_INTERVAL)
-      return cg_fail(CG_EINVAL, fn + ": rule " + std::to_string(r) + ": kind " + std::to_string(kind[r]) +
-                                    " is not CG_JOB_COMMON, CG_JOB_ALONE or CG_JOB_INTERVAL");
-    if (unit && r > 0 && unit[r] < unit[r - 1])
-      return cg_fail(CG_EINVAL, fn + ": rule " + std::to_string(r) + ": unit decreases");
-  }
-  out->what = what;
-  out->lock_ttl = lock_ttl;
-  out->units.clear();
-  out->flag.assign(size_t(R), 0);
-  out->dsec.clear();
-  if (out->running()) {
-    out->dsec.resize(size_t(R));
-    for (int64_t r = 0; r < R; r++)
-      out->dsec[size_t(r)] = inflight_seconds(std::max<int64_t>(avg_ms[r], 0), horizon);
-  }
-  for (int64_t r0 = 0; r0 < R;) {
-    int64_t r1 = r0 + 1;
-    if (unit)
-      for (; r1 < R && unit[r1] == unit[r0]; r1++)
-        if (kind[r1] != kind[r0] || avg_ms[r1] != avg_ms[r0])
-          return cg_fail(CG_EINVAL, fn + ": rule " + std::to_string(r1) + ": kind / avg_time_ms differ inside unit " +
-                                        std::to_string(unit[r0]));
-    if (kind[r0] != CG_JOB_COMMON) {
-      if (r1 - r0 > INT32_MAX) return cg_fail(CG_ERANGE, fn + ": rule " + std::to_string(r0) + ": unit too long");
-      bool any = false;
-      for (int64_t r = r0; r < r1; r++)
-        if (!contends || contends[r]) any = true, out->flag[size_t(r)] = 1;
-      if (any)
-        out->units.push_back(LockUnit{r0, avg_ms[r0], inflight_seconds(std::max<int64_t>(avg_ms[r0], 0), horizon),
-                                      int32_t(r1 - r0), kind[r0]});
-    }
-    r0 = r1;
-  }
   return CG_OK;
 }
 

@@ -26,6 +26,9 @@ seen from Python.  Wraps a cg_ctx (one HIP device + stream + HBM buffers).
                                             fires the KindAlone / KindInterval lock grants / skips
   Engine.lock_runs_per_node(specs, loc, t0, width, n_buckets, kind, avg_time_ms, unit, contends, drules, mode, lock_ttl, what)
                                             ... per (node, bucket)
+  Engine.expand_verdicts(specs, loc, t0, t1, admit, lock)
+                                            expand() plus one byte per fire: dropped / lock-skipped
+  Engine.verdicts_select(mask, value)       rule-major CSR of the fires with those bits
   Engine.profile_node_peaks()               per node: largest cell, first bucket with it
   Engine.profile_top_rules(k, buckets=None) per node: the k rules with the largest
                                             cells of one bucket (default: its peak)
@@ -1086,6 +1089,108 @@ class Engine:
         buf = (C.c_float * 23)()
         check(lib().cg_last_kernel_times(self._h, buf, 23))
         return buf[22]
+
+    # ---------------------------------------------------- fire verdicts
+    def _verdict_args(self, n, admit, lock):
+        """(cg_admit_args or None, cg_lock_args or None, arrays to keep alive)
+        of a verdict call: admit = (dur_ms, parallels, unit), lock = (kind,
+        avg_time_ms, unit, contends, lock_ttl)."""
+        keep, a, l = [], None, None
+        if admit is not None:
+            dur_ms, parallels, unit = admit
+            d, p, u, _ = self._admit_args(n, dur_ms, parallels, unit, "dropped")
+            a = _lib.cg_admit_args(d.ctypes.data, p.ctypes.data, self._ptr(u))
+            keep += [d, p, u]
+        if lock is not None:
+            kind, avg_time_ms, unit, contends, lock_ttl = lock
+            k, av, u, c = self._lock_arrays(n, kind, avg_time_ms, unit, contends)
+            l = _lib.cg_lock_args(k.ctypes.data, av.ctypes.data, self._ptr(u), self._ptr(c), int(lock_ttl))
+            keep += [k, av, u, c]
+        return a, l, keep
+
+    def _lock_arrays(self, n, kind, avg_time_ms, unit, contends):
+        # _lock_args without its lock_ttl check: the library's code and message are the call's
+        k, a, u, c, _, _ = self._lock_args(n, kind, avg_time_ms, unit, contends, 2, "skipped")
+        return k, a, u, c
+
+    def expand_verdicts_device(self, specs, loc, t0, t1, admit=None, lock=None):
+        """expand_device() plus one verdict byte per fire, left in HBM
+        (cg_expand_verdicts_device): the event total.  Bit 0
+        (_lib.VERDICT_DROPPED): Job.limit() would drop the fire, given admit =
+        (dur_ms, parallels, unit) as admit() takes them; bit 1
+        (_lib.VERDICT_SKIPPED): the KindAlone / KindInterval lock would skip
+        it, given lock = (kind, avg_time_ms, unit, contends, lock_ttl) as
+        lock_runs() takes them.  The two bits are independent, as the two
+        profiles are.  The call replaces the engine's expansion result
+        (result_device, copy_times) and leaves the profile alone."""
+        a, l, keep = self._verdict_args(specs.n, admit, lock)
+        n = C.c_int64()
+        check(lib().cg_expand_verdicts_device(self._h, specs._h, self._loc(loc).handle, int(t0), int(t1),
+                                              None if a is None else C.byref(a), None if l is None else C.byref(l),
+                                              C.byref(n)))
+        del keep
+        self._verdict_rules = specs.n  # sel_off of a later verdicts_select has one more entry
+        return n.value
+
+    def expand_verdicts(self, specs, loc, t0, t1, admit=None, lock=None):
+        """(offsets int64 [R+1], times int64 [E], verdict uint8 [E]) of
+        expand_verdicts_device(), copied to the host."""
+        sp = self._specs(specs)
+        try:
+            n = self.expand_verdicts_device(sp, loc, t0, t1, admit, lock)
+            off = np.empty(sp.n + 1, dtype=np.int64)
+            check(lib().cg_result_copy_offsets(self._h, off.ctypes.data))
+            return off, self.copy_times(0, n), self.verdicts_copy(0, n)
+        finally:
+            if sp is not specs:  # uploaded here: the result does not read it
+                sp.free()
+
+    def verdicts_device(self):
+        """(device pointer of the verdict bytes, event total); CgError
+        (CG_EINVAL) when no verdict call succeeded or a later expansion call
+        replaced its result."""
+        p, n = C.c_void_p(), C.c_int64()
+        check(lib().cg_verdicts_device(self._h, C.byref(p), C.byref(n)))
+        return p.value, n.value
+
+    def verdicts_copy(self, first, count):
+        out = np.empty(max(count, 1), dtype=np.uint8)
+        check(lib().cg_verdicts_copy(self._h, int(first), int(count), out.ctypes.data))
+        return out[:count]
+
+    def verdicts_select_device(self, mask, value):
+        """Selects the fires with (verdict & mask) == value on the device
+        (cg_verdicts_select_device): their count."""
+        n = C.c_int64()
+        check(lib().cg_verdicts_select_device(self._h, int(mask), int(value), C.byref(n)))
+        return n.value
+
+    def verdicts_selected_device(self):
+        """(sel_off pointer, sel_times pointer, count) of the last selection."""
+        o, t, n = C.c_void_p(), C.c_void_p(), C.c_int64()
+        check(lib().cg_verdicts_selected_device(self._h, C.byref(o), C.byref(t), C.byref(n)))
+        return o.value, t.value, n.value
+
+    def verdicts_select(self, mask, value, n_rules=None):
+        """(sel_off int64 [R+1], sel_times int64 [n]): the rule-major CSR of
+        the fires with (verdict & mask) == value, ascending per rule.  mask 1:
+        by Job.limit(), 2: by the lock, 3: both bits."""
+        n = self.verdicts_select_device(mask, value)
+        if n_rules is None:
+            n_rules = self._verdict_rules
+        off = np.empty(n_rules + 1, dtype=np.int64)
+        check(lib().cg_verdicts_selected_copy_offsets(self._h, off.ctypes.data))
+        times = np.empty(max(n, 1), dtype=np.int64)
+        check(lib().cg_verdicts_selected_copy_times(self._h, 0, n, times.ctypes.data))
+        return off, times[:n]
+
+    def verdict_times(self):
+        """ms of the last verdict call and selection (cg_verdict_times):
+        expansion, init pass, admission walk, lock walk, selection count +
+        scan, selection write."""
+        buf = (C.c_float * 6)()
+        k = lib().cg_verdict_times(self._h, buf, 6)
+        return list(buf)[:max(k, 0)]
 
     def profile_kind(self):
         """What the readable profile holds: _lib.PROFILE_STARTS,

@@ -313,6 +313,48 @@ class JobSet(_Interned):
         return job_lock_runs_of(eng, eng.upload(self.schedules()), self.rules_in(), t0, width, n_buckets, kind, avg,
                                 loc, mode, lock_ttl, lambda j: self.jobs[j].ID)
 
+    def fire_verdicts(self, t0, t1, loc=None, mode=_lib.EXCLUDE_NONE, lock_ttl=300, engine=None):
+        """Every fire of every rule over (t0, t1] with its verdict
+        (Engine.expand_verdicts): (offsets int64 [R+1], times int64 [E],
+        verdict uint8 [E], the IDs of the jobs that were split).  Bit 0
+        (_lib.VERDICT_DROPPED): Job.limit() would drop the fire -- a failure
+        notice; bit 1 (_lib.VERDICT_SKIPPED): the job's KindAlone /
+        KindInterval lock is still held and the job runs on no node.  The
+        arguments are node_drops' (rule_durations, rule_parallels,
+        admission_units: a split job's rules are limited one by one) and
+        node_lock_skips' (rule_kinds, lock_units, Engine.rule_contends); the
+        two bits are independent and inherit those profiles' limits."""
+        from .engine import default_engine
+        eng = engine or default_engine()
+        rin = self.rules_in()
+        off, times, verdict, split = fire_verdicts_of(self, eng, rin, t0, t1, loc, mode, lock_ttl)
+        return off, times, verdict, [self.jobs[j].ID for j in split]
+
+    def node_failures(self, nid, t0, t1, loc=None, mode=_lib.EXCLUDE_NONE, lock_ttl=300, engine=None):
+        """The fires of node nid's Cmds over (t0, t1] that will not run:
+        [(time, job ID, rule ID, "dropped" | "skipped" | "dropped+skipped"),
+        ...] in (time, rule) order -- the selection of the fires with a verdict
+        bit set (Engine.verdicts_select), restricted on the host to the rules
+        the node runs under the exclude mode.  Limits as fire_verdicts."""
+        from .engine import default_engine
+        eng = engine or default_engine()
+        rin = self.rules_in()
+        n = self.node_index(nid)
+        if n < 0:
+            raise KeyError(f"unknown node {nid!r}")
+        rn_off, rn_nodes = eng.rule_nodes(rin, mode)
+        rule_of_pair = np.repeat(np.arange(rin.n_rules), np.diff(rn_off))
+        mine = np.unique(rule_of_pair[rn_nodes == n])
+        fire_verdicts_of(self, eng, rin, t0, t1, loc, mode, lock_ttl)
+        # one selection per bit; a fire in both lists carries both
+        what = {}
+        for mask, name in ((_lib.VERDICT_DROPPED, "dropped"), (_lib.VERDICT_SKIPPED, "skipped")):
+            sel_off, sel_times = eng.verdicts_select(mask, mask)
+            for r in mine.tolist():
+                for t in sel_times[int(sel_off[r]):int(sel_off[r + 1])].tolist():
+                    what[(t, r)] = what[(t, r)] + "+" + name if (t, r) in what else name
+        return [(t, self.jobs[self.rule_job[r]].ID, self.rules[r].ID, what[(t, r)]) for t, r in sorted(what)]
+
     def node_inflight(self, t0, width, n_buckets, loc=None, mode=_lib.EXCLUDE_NONE, engine=None):
         """Commands running per node at each bucket edge t0 + (b+1)*width
         (Engine.inflight_per_node), each rule running for its job's AvgTime
@@ -444,6 +486,22 @@ def lock_skips_of(js, eng, specs, rin, t0, width, n_buckets, kind, avg, loc, mod
     finally:
         specs.free()
     return {js.node_id(n): counts[n] for n in range(rin.n_nodes)}
+
+
+def fire_verdicts_of(js, eng, rin, t0, t1, loc, mode, lock_ttl):
+    """fire_verdicts of a job set: (offsets, times, verdict, split job
+    indices); the verdicts stay selectable on the engine."""
+    dur, _ = js.rule_durations()
+    unit, split = admission_units(rin, mode)
+    kind, avg = js.rule_kinds()
+    contends = eng.rule_contends(rin, mode)
+    specs = eng.upload(js.schedules())
+    try:
+        off, times, verdict = eng.expand_verdicts(specs, loc, t0, t1, admit=(dur, js.rule_parallels(), unit),
+                                                  lock=(kind, avg, lock_units(rin), contends, lock_ttl))
+    finally:
+        specs.free()
+    return off, times, verdict, split
 
 
 def job_lock_runs_of(eng, specs, rin, t0, width, n_buckets, kind, avg, loc, mode, lock_ttl, job_id):

@@ -922,6 +922,113 @@ int cg_profile_kind(cg_ctx* ctx, int* kind);
 int cg_profile_node_peaks(cg_ctx* ctx, int32_t first_node, int32_t count, int64_t* peak /* [count] */,
                           int32_t* bucket /* [count] */);
 
+/* ---------------------------------------------------------- fire verdicts --- */
+/* Which fires those are.  The admission and lock profiles count, per bucket,
+ * the fires Job.limit() drops (job.go:134-139, 165-187: a failure notice each,
+ * j.Fail) and the fires the KindAlone / KindInterval lock skips (job.go:194-271:
+ * a run that silently does not happen).  A verdict call marks them in the fire
+ * list itself: it leaves the result of cg_expand_device(ctx, specs, z, t0, t1)
+ * -- offsets[R+1], times[E], rule-major, ascending per rule, bit-identical --
+ * plus verdict[E], one uint8 per fire: verdict[e] for e in [offsets[r],
+ * offsets[r+1]) belongs to fire times[e] of rule r.
+ *
+ *   CG_VERDICT_DROPPED (bit 0)  set iff `admit` was given and the admission
+ *     profile's literal process, run over (t0, t1], drops this fire
+ *     (job.go:165-187): units are the maximal runs of equal unit[], a unit's
+ *     fires are taken in (time, rule index) order, and a fire at t is admitted
+ *     iff P == 0 or fewer than P admitted fires a of the unit have
+ *     a*1000 + dur_ms > t*1000; d is dur_ms rounded up to whole seconds and
+ *     clamped to t1 - t0.  Fires of units that never drop get 0.
+ *   CG_VERDICT_SKIPPED (bit 1)  set iff `lock` was given and the lock profile's
+ *     literal process skips this fire (job.go:235-271): t < free_at, or ttl == 0
+ *     with ttl = lockTtl at now = t (job.go:194-233); a granted fire sets
+ *     free_at = t + ttl (INTERVAL) or t + d + ttl (ALONE).  Fires of COMMON
+ *     units and of non-contending rules get 0.
+ *   Bits 2..7 are zero.  Every byte of verdict[0..E) is written by every call.
+ *
+ * The two bits are independent, exactly as the two profiles are: limit() and
+ * lock() are not composed, and every limit the admission and lock profiles list
+ * under "Not reproduced" is inherited unchanged (cold start at t0, same-second
+ * order by rule index, which node wins a lock, Parallels of INTERVAL jobs,
+ * Retry / Interval, actual run times, clock skew).  With t1 = t0 + B*w, binning
+ * the fires with bit 0 set gives cg_admit_device(what = CG_PROFILE_DROPPED) cell
+ * by cell and those without it CG_PROFILE_ADMITTED; the same holds for bit 1
+ * with CG_PROFILE_LOCK_SKIPPED / CG_PROFILE_LOCK_GRANTED.
+ *
+ * cg_expand_verdicts_device is an expansion call: synchronous on the ctx
+ * stream, it drains pending pipelined calls as cg_expand_device does and
+ * replaces the readable expansion result (cg_result_device and cg_result_copy_*
+ * serve it); the readable profile is untouched.  The argument structs hold host
+ * arrays [R] owned by the caller, copied inside the call and not retained; their
+ * members are cg_admit_device's and cg_lock_profile_device's, with the same
+ * checks, messages and codes: a negative duration or parallels, a decreasing
+ * unit, values that differ inside a unit, a kind that is none of the three
+ * (CG_EINVAL naming the first rule), lock_ttl < 2 (CG_EINVAL), parallels above
+ * CG_ADMIT_MAX_PARALLELS in a unit that can drop (CG_ERANGE).  Both structs
+ * NULL, or t1 <= t0: CG_EINVAL; a horizon above CG_MAX_HORIZON: CG_ERANGE.  All
+ * of these are raised before any device work and leave the previous results
+ * readable.  A stuck rule (CG_ERANGE, as cg_expand_device), a granted fire
+ * whose Next never returns (CG_ERANGE, as the lock profile) and a plan that
+ * leaves too little LDS for the admission ring or the walked runs' positions
+ * (CG_ERANGE) fail the call and leave no verdicts readable.  The walks check
+ * every position against the fire list before they store; a mismatch fails the
+ * call with CG_EHIP ("verdict position mismatch").  R = 0 and E = 0 are valid;
+ * E may exceed 2^32.
+ *
+ * The accessors below return CG_EINVAL until a verdict call has succeeded, and
+ * again once any later expansion call on the ctx (synchronous, pipelined,
+ * per-node, count or profile) has replaced the result the bytes belong to. */
+#define CG_VERDICT_DROPPED 1
+#define CG_VERDICT_SKIPPED 2
+/* Job.AvgTime, Job.Parallels after alone() and the admission unit per rule
+ * (job.go:165-187, 378-387); host [R]; unit may be NULL */
+typedef struct {
+  const int64_t* dur_ms;
+  const int64_t* parallels;
+  const int32_t* unit;
+} cg_admit_args;
+/* Job.Kind, Job.AvgTime, the lock unit (the job: the key is Job.ID,
+ * job.go:235-271) and whether the rule reaches the lock, per rule, and
+ * conf.Config.LockTtl (job.go:194-233); host [R]; unit, contends may be NULL */
+typedef struct {
+  const int32_t* kind;
+  const int64_t* avg_time_ms;
+  const int32_t* unit;
+  const uint8_t* contends;
+  int64_t lock_ttl;
+} cg_lock_args;
+/* the expansion over (t0, t1] with its verdict bytes (job.go:134-147: limit(),
+ * then lock()); admit or lock may be NULL, not both */
+int cg_expand_verdicts_device(cg_ctx* ctx, const cg_specs* specs, const cg_zone* z, int64_t t0, int64_t t1,
+                              const cg_admit_args* admit, const cg_lock_args* lock, int64_t* n_events);
+/* the bytes in device memory, valid until the next verdict or expansion call
+ * (job.go:134-147); either pointer may be NULL */
+int cg_verdicts_device(cg_ctx* ctx, const uint8_t** d_verdict, int64_t* n_events);
+/* verdict[first, first + count) to the host (job.go:134-147) */
+int cg_verdicts_copy(cg_ctx* ctx, int64_t first, int64_t count, uint8_t* out);
+/* The rule-major CSR of the fires with (verdict & mask) == value: sel_off[R+1],
+ * sel_times[*n_selected], ascending per rule.  mask 1: by limit()
+ * (job.go:165-187), 2: by lock() (job.go:235-271), 3: both; mask outside 1..3 or
+ * value & ~mask != 0: CG_EINVAL.  The selection stays readable until the next
+ * verdict, select or expansion call. */
+int cg_verdicts_select_device(cg_ctx* ctx, int mask, int value, int64_t* n_selected);
+/* the last selection in device memory / copied to the host (job.go:134-147);
+ * CG_EINVAL when there is none */
+int cg_verdicts_selected_device(cg_ctx* ctx, const int64_t** d_sel_off, const int64_t** d_sel_times,
+                                int64_t* n_selected);
+/* sel_off [R+1] of the last selection to the host (job.go:134-147) */
+int cg_verdicts_selected_copy_offsets(cg_ctx* ctx, int64_t* out);
+/* sel_times[first, first + count) of the last selection to the host (job.go:134-147) */
+int cg_verdicts_selected_copy_times(cg_ctx* ctx, int64_t first, int64_t count, int64_t* out);
+/* ms of the last verdict call and the last selection: the expansion (the whole
+ * cg_expand_device chain with its host synchronise, plus this call's uploads of
+ * the rule flags and the compacted units), the init pass, the admission walk
+ * (job.go:165-187), the lock walk (job.go:235-271), the selection's count +
+ * scan and its write; returns the count written (<= 6).  The first four are set
+ * by a verdict call that succeeds and read 0 after one that fails; the last two
+ * are set by a selection and cleared by the next verdict call. */
+int cg_verdict_times(cg_ctx* ctx, float* ms, int n);
+
 /* ---------------------------------------------- top rules of a bucket ---- */
 /* Which rules make up a cell of the node matrix (or a bucket total): the peaks
  * say that a node will run 900 commands at 09:00, these calls say which rules
