@@ -500,7 +500,7 @@ int cg_set_node_order(cg_ctx* c, int order) {
 
 int cg_last_kernel_times(cg_ctx* c, float* ms, int n) {
   if (!c || !ms) return cg_fail(CG_EINVAL, "cg_last_kernel_times: null");
-  int k = std::min(n, int(sizeof(c->kt) / sizeof(c->kt[0])));
+  int k = std::min(n, int(KT_COUNT));
   for (int i = 0; i < k; i++) ms[i] = c->kt[i];
   return k;
 }

@@ -233,6 +233,69 @@ struct PnAsyncSet {
   }
 };
 
+// Slots of cg_ctx::kt, the milliseconds cg_last_kernel_times reports.  The
+// values are public: engine.py and the tools read the slots by number.
+enum Kt {
+  KT_X_COUNT = 0,        // expansion: k_count
+  KT_X_SCAN = 1,         // scan of the run counts
+  KT_X_MAP = 2,          // slice map
+  KT_X_WRITE_CF = 3,     // k_write_cf (pipelined calls: the mean of the calls checked)
+  KT_X_WRITE_WALK = 4,   // k_write_walk
+  KT_X_OFFSETS = 5,      // per-rule offsets (0: written by the scan)
+  KT_PN_JOIN = 6,        // last per-node call: rule->node join
+  KT_PN_TRANSPOSE = 7,   // transpose + per-node offsets
+  KT_PN_WRITE = 8,       // k_node_write (pipelined windows: the mean of the calls checked)
+  KT_DISP_SCAN = 9,      // last cg_dispatcher_fire: scan
+  KT_DISP_DUE = 10,      // due compaction
+  KT_DISP_ADVANCE = 11,  // advance
+  KT_TIME_ORDER = 12,    // time-order pass of the last cg_node_result_order_by_time
+  KT_FANOUT = 13,        // last cg_dispatcher_fanout
+  KT_PF_RULES = 14,      // last profile call: k_profile_rules / k_inflight_rules
+  KT_PF_WALK = 15,       // k_profile_walk / k_inflight_walk (a unit call: up to k_admit_prepare)
+  KT_PF_TOTALS = 16,     // k_profile_totals
+  KT_PF_JOIN = 17,       // join + transpose (0: the cached one was reused)
+  KT_PF_NODES = 18,      // node matrix
+  KT_UNIT_PREPARE = 19,  // k_admit_prepare of an admission or lock call (0 after any other)
+  KT_ADMIT_UNITS = 20,   // k_admit_units
+  KT_LOCK_UNITS = 21,    // k_lock_units
+  KT_ROWS_PREFIX = 22,   // k_rows_prefix of a RUNNING call
+  KT_COUNT
+};
+static_assert(KT_COUNT == 23, "cg_last_kernel_times' slots are public");
+// cg_ctx::pfev: where a profile call records each event on the ctx stream
+enum PfEv {
+  PFEV_RULES = 0,      // before the rule-matrix kernel
+  PFEV_WALK = 1,       // before the walked runs' kernel
+  PFEV_TOTALS = 2,     // before k_profile_totals: the end of the unit walk, in a RUNNING call of k_rows_prefix
+  PFEV_TOTALS_END = 3, // where a per-node call's join starts
+  PFEV_NODES = 4,      // before the node matrix
+  PFEV_NODES_END = 5,
+  PFEV_PREPARE = 6,    // before k_admit_prepare
+  PFEV_UNITS = 7,      // before the unit walk
+  PFEV_PREFIX = 8,     // RUNNING calls: the end of the unit walk, before k_rows_prefix
+  PFEV_COUNT
+};
+// cg_ctx::vdev: a verdict call's events, then a selection's
+enum VdEv {
+  VDEV_EXPAND = 0,     // before the plain expansion
+  VDEV_INIT = 1,       // before k_verdict_init (behind the uploads)
+  VDEV_ADMIT = 2,      // before k_admit_verdicts
+  VDEV_LOCK = 3,       // before k_lock_verdicts
+  VDEV_WALKS_END = 4,
+  VDEV_SEL_COUNT = 5,  // before k_verdict_count
+  VDEV_SELECT = 6,     // after the count's scan; recorded again before k_verdict_select
+  VDEV_SELECT_END = 7,
+  VDEV_COUNT
+};
+
+// the timing events of one entry-point family, created on first use
+template <size_t N>
+int ensure_events(hipEvent_t (&evs)[N]) {
+  for (hipEvent_t& e : evs)
+    if (!e) HIPCHK(hipEventCreateWithFlags(&e, hipEventDisableSystemFence));
+  return CG_OK;
+}
+
 struct cg_ctx {
   int device = 0;
   int write_blocks = 1024;  // persistent k_write_cf grid (set from the CU count)
@@ -241,20 +304,9 @@ struct cg_ctx {
   hipEvent_t ev[8] = {};
   hipEvent_t pev[4] = {};  // per-node phases
   std::mutex mu;
-  // ms: [0..5] expansion phases (count, scan, map, write_cf, write_walk,
-  // offsets), [6..8] per-node phases (rule->node join, transpose + per-node
-  // offsets, k_node_write) of the last per-node call, [9..11] dispatcher
-  // wake (scan, due compaction, advance) of the last cg_dispatcher_fire, [12]
-  // the time-order pass of the last cg_node_result_order_by_time, [13] the
-  // last cg_dispatcher_fanout, [14..18] the last profile call (k_profile_rules,
-  // k_profile_walk, k_profile_totals, join + transpose when rebuilt, the
-  // node matrix; of an in-flight call k_inflight_rules and k_inflight_walk
-  // in the first two), [19..20] the last admission profile's own kernels
-  // (k_admit_prepare, k_admit_units; 0 after any other profile call), [21]
-  // the last lock profile's unit walk (k_lock_units; its k_admit_prepare in [19])
-  float kt[23] = {0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0};
-  // expansion phase timing: 2 = an event between every phase (kt[0..5]);
-  // 1 = events around k_write_cf only (kt[3]; the others read -1).  Each
+  float kt[KT_COUNT] = {};  // cg_last_kernel_times: ms per slot (enum Kt)
+  // expansion phase timing: 2 = an event between every phase (KT_X_COUNT..KT_X_OFFSETS);
+  // 1 = events around k_write_cf only (KT_X_WRITE_CF; the others read -1).  Each
   // event recorded between two kernels costs 6-12 us of idle GPU on this
   // stack, so throughput runs use 1 (cg_set_phase_timing).
   int phase_timing = 2;
@@ -277,20 +329,16 @@ struct cg_ctx {
   uint64_t res_gen = 0;
 
   // fire verdicts (cg_verdict.hip): one byte per fire of the rule-major result
-  // of generation vd_gen (vd_R rules, vd_E fires), the per-call uploads of the
-  // walks (rule flags = initial verdict bytes, the lock walk's contends, the
-  // compacted units), a device error word {position mismatch, stuck rule}, and
-  // the last selection (sel_off [vd_R + 1], sel_times [vd_nsel])
-  DBuf<uint8_t> vd_verdict, vd_flag, vd_contends;
-  DBuf<char> vd_admit_units, vd_lock_units;
-  DBuf<unsigned long long> vd_err;
+  // of generation vd_gen (vd_R rules, vd_E fires), and the last selection
+  // (sel_off [vd_R + 1], sel_times [vd_nsel])
+  DBuf<uint8_t> vd_verdict;
   DBuf<int32_t> vd_sel_cnt;
   DBuf<int64_t> vd_sel_off, vd_sel_times;
   uint64_t vd_gen = 0;
   int64_t vd_R = 0, vd_E = 0, vd_nsel = 0;
   bool vd_valid = false, vd_sel_valid = false;
   float vd_ms[6] = {0, 0, 0, 0, 0, 0};  // cg_verdict_times
-  hipEvent_t vdev[8] = {};
+  hipEvent_t vdev[VDEV_COUNT] = {};
 
   // pipelined expansion (cg_async.cpp): the sets used in turn, count + scan
   // on st_cs, writers on st / st_w1; as_last = set of the last async result
@@ -397,16 +445,18 @@ struct cg_ctx {
   DBuf<int64_t> pf_dur, pf_peak;
   DBuf<int32_t> pf_peak_bucket;
   bool pf_peaks_valid = false;
-  // an admission call's compacted units that can drop (cg::AdmitUnit, 24 B
-  // each) and its per-rule "unit can drop" flags [R], uploaded per call; of a
-  // lock profile the compacted lock units (cg::LockUnit, 32 B each) and the
-  // "contending rule of a lock unit" flags
-  DBuf<char> pf_admit_units;
-  DBuf<uint8_t> pf_admit_flag;
-  // k_lock_units lowers it from ~0 to a rule whose Next never returns (set before every launch)
-  DBuf<unsigned long long> pf_lock_stuck;
-  hipEvent_t pfev[9] = {};  // created by the first profile call ([6], [7]: around k_admit_prepare; the unit walk ends at [2],
-                            // in a RUNNING call at [8] with k_rows_prefix between [8] and [2])
+  // The per-call uploads of a unit walk (cg_units.h, unit_upload), shared by
+  // the profile and the verdict calls: every user holds mu for the whole call
+  // and nothing reads them once it has ended.  Slot 0 admission, slot 1 lock
+  // (a verdict call walks both): the compacted units (cg::AdmitUnit 24 B,
+  // cg::LockUnit 32 B each), per-rule flags [R] ([0] "unit can drop", of a
+  // verdict call the initial verdict bytes; [1] "contending rule of a lock
+  // unit") and two error words the kernels lower from ~0 ([0] verdict position
+  // mismatch, [1] the lock walk's rule whose Next never returns)
+  DBuf<char> uw_units[2];
+  DBuf<uint8_t> uw_flag[2];
+  DBuf<unsigned long long> uw_err;
+  hipEvent_t pfev[PFEV_COUNT] = {};  // created by the first profile call
   // The node matrix is summed over nt_off / nt_rule, which are the per-node
   // path's cache and may be rebuilt under a readable profile: nt_gen counts
   // the rebuilds (transpose_locked, and the dispatcher bind that takes the
@@ -459,11 +509,11 @@ struct cg_ctx {
     pf_rules.release(); pf_chunk_cnt.release(); pf_totals.release(); pf_nodes.release();
     pf_part.release(); pf_chunk_off.release();
     pf_dur.release(); pf_peak.release(); pf_peak_bucket.release();
-    pf_admit_units.release(); pf_admit_flag.release(); pf_lock_stuck.release();
+    for (int i = 0; i < 2; i++) uw_units[i].release(), uw_flag[i].release();
+    uw_err.release();
     for (hipEvent_t& e : pfev)
       if (e) (void)hipEventDestroy(e), e = nullptr;
-    vd_verdict.release(); vd_flag.release(); vd_contends.release(); vd_admit_units.release();
-    vd_lock_units.release(); vd_err.release(); vd_sel_cnt.release(); vd_sel_off.release(); vd_sel_times.release();
+    vd_verdict.release(); vd_sel_cnt.release(); vd_sel_off.release(); vd_sel_times.release();
     for (hipEvent_t& e : vdev)
       if (e) (void)hipEventDestroy(e), e = nullptr;
   }

@@ -223,8 +223,8 @@ int cg_expand_wait(cg_ctx* c, int64_t* n_events) {
   int rc = async_drain(c);
   if (rc) return rc;
   if (c->wr_n > 0) {
-    c->kt[3] = float(c->wr_ms_sum / c->wr_n);  // mean writer time of the calls checked (check_set)
-    for (int i : {0, 1, 2, 4, 5}) c->kt[i] = -1.f;
+    c->kt[KT_X_WRITE_CF] = float(c->wr_ms_sum / c->wr_n);  // mean writer time of the calls checked (check_set)
+    for (int i : {KT_X_COUNT, KT_X_SCAN, KT_X_MAP, KT_X_WRITE_WALK, KT_X_OFFSETS}) c->kt[i] = -1.f;
   }
   c->wr_ms_sum = 0;
   c->wr_n = 0;

@@ -217,9 +217,9 @@ int cg_dispatcher_fire(cg_dispatcher* d, int64_t now, int64_t* n_due, int64_t* e
   HIPCHK(hipGetLastError());
   DispatchState h;
   rc = d->read_state(&h);
-  (void)hipEventElapsedTime(&c->kt[9], c->pev[0], c->pev[1]);
-  (void)hipEventElapsedTime(&c->kt[10], c->pev[1], c->pev[2]);
-  (void)hipEventElapsedTime(&c->kt[11], c->pev[2], c->pev[3]);
+  (void)hipEventElapsedTime(&c->kt[KT_DISP_SCAN], c->pev[0], c->pev[1]);
+  (void)hipEventElapsedTime(&c->kt[KT_DISP_DUE], c->pev[1], c->pev[2]);
+  (void)hipEventElapsedTime(&c->kt[KT_DISP_ADVANCE], c->pev[2], c->pev[3]);
   d->n_due = int64_t(h.n_due);
   *n_due = d->n_due;
   *effective = d->effective;

@@ -121,7 +121,7 @@ int sync_count_scan(cg_ctx* c, const cg_specs* s, const cg_zone* z, int64_t t0, 
   HIPCHK(hipSetDevice(c->device));
   if (t1 - t0 > CG_MAX_HORIZON || t0 < -(int64_t(1) << 45) || t1 > (int64_t(1) << 45))
     return cg_fail(CG_ERANGE, "horizon must satisfy t1 - t0 <= CG_MAX_HORIZON (40 years)");
-  for (int i = 0; i < 6; i++) c->kt[i] = 0;
+  for (int i = KT_X_COUNT; i <= KT_X_OFFSETS; i++) c->kt[i] = 0;
   int rc = run_set_count_scan(c->rs, s, z, t0, t1, map_cap, c->st, c->phase_timing >= 2 ? c->ev : nullptr, empty,
                               lock_table);
   if (rc) return rc;
@@ -181,15 +181,15 @@ int expand_device_locked(cg_ctx* c, const cg_specs* s, const cg_zone* z, int64_t
     if (E <= cap) break;
     if ((rc = c->times.ensure(E))) return rc;  // grow and redo the write phase
   }
-  (void)hipEventElapsedTime(&c->kt[3], c->ev[4], c->ev[5]);
+  (void)hipEventElapsedTime(&c->kt[KT_X_WRITE_CF], c->ev[4], c->ev[5]);
   if (all_phases) {
-    (void)hipEventElapsedTime(&c->kt[0], c->ev[0], c->ev[1]);
-    (void)hipEventElapsedTime(&c->kt[1], c->ev[1], c->ev[2]);
-    (void)hipEventElapsedTime(&c->kt[2], c->ev[3], c->ev[4]);
-    (void)hipEventElapsedTime(&c->kt[4], c->ev[5], c->ev[6]);
-    c->kt[5] = 0.f;  // per-rule offsets: written by the scan (k_scan_apply)
+    (void)hipEventElapsedTime(&c->kt[KT_X_COUNT], c->ev[0], c->ev[1]);
+    (void)hipEventElapsedTime(&c->kt[KT_X_SCAN], c->ev[1], c->ev[2]);
+    (void)hipEventElapsedTime(&c->kt[KT_X_MAP], c->ev[3], c->ev[4]);
+    (void)hipEventElapsedTime(&c->kt[KT_X_WRITE_WALK], c->ev[5], c->ev[6]);
+    c->kt[KT_X_OFFSETS] = 0.f;  // per-rule offsets: written by the scan (k_scan_apply)
   } else {
-    c->kt[0] = c->kt[1] = c->kt[2] = c->kt[4] = c->kt[5] = -1.f;
+    c->kt[KT_X_COUNT] = c->kt[KT_X_SCAN] = c->kt[KT_X_MAP] = c->kt[KT_X_WRITE_WALK] = c->kt[KT_X_OFFSETS] = -1.f;
   }
   c->last_R = R;
   c->last_E = E;

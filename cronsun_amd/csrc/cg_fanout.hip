@@ -669,7 +669,7 @@ int cg_dispatcher_fanout(cg_dispatcher* d, int64_t* n_pairs) {
   HIPCHK(hipSetDevice(c->device));
   f.valid = false;
   f.n_pairs = 0;
-  c->kt[13] = 0.f;
+  c->kt[KT_FANOUT] = 0.f;
   int rc = f.node_off.ensure(size_t(f.N) + 1);
   if (rc) return rc;
   if (d->n_due == 0 || f.nnz == 0) {
@@ -689,7 +689,7 @@ int cg_dispatcher_fanout(cg_dispatcher* d, int64_t* n_pairs) {
   if (rc) return rc;
   (void)hipEventRecord(c->pev[1], c->st);
   HIPCHK(hipStreamSynchronize(c->st));
-  (void)hipEventElapsedTime(&c->kt[13], c->pev[0], c->pev[1]);
+  (void)hipEventElapsedTime(&c->kt[KT_FANOUT], c->pev[0], c->pev[1]);
   f.valid = true;
   *n_pairs = f.n_pairs;
   return CG_OK;

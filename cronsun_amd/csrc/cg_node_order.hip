@@ -1360,7 +1360,7 @@ extern "C" int cg_node_result_order_by_time(cg_ctx* c) {
   if (pn_async_pending(c))
     return cg_fail(CG_EINVAL, "pipelined per-node windows pending (call cg_expand_per_node_wait first)");
   if (c->pn_time_ordered) {  // written in (time, rule) order already
-    c->kt[12] = 0.f;
+    c->kt[KT_TIME_ORDER] = 0.f;
     return CG_OK;
   }
   if ((rc = order_by_time_locked(c))) {  // a failed pass may leave the lists half permuted
@@ -1403,7 +1403,7 @@ int order_by_time_locked(cg_ctx* c, int in_mode) {
     (void)hipEventRecord(c->pev[1], st);
     if ((rc = cg_hip_check(hipStreamSynchronize(st), "sync"))) return rc;
     if (c->pn.res_host[2]) return cg_fail(CG_EHIP, kOrderCheckMsg);
-    (void)hipEventElapsedTime(&c->kt[12], c->pev[0], c->pev[1]);
+    (void)hipEventElapsedTime(&c->kt[KT_TIME_ORDER], c->pev[0], c->pev[1]);
     c->pn_time_ordered = true;
     return CG_OK;
   }
@@ -1443,7 +1443,7 @@ int order_by_time_locked(cg_ctx* c, int in_mode) {
     std::swap(c->node_rule, c->node_rule2);
   }
   if ((rc = cg_hip_check(hipStreamSynchronize(st), "sync"))) return rc;
-  (void)hipEventElapsedTime(&c->kt[12], c->pev[0], c->pev[1]);
+  (void)hipEventElapsedTime(&c->kt[KT_TIME_ORDER], c->pev[0], c->pev[1]);
   c->pn_time_ordered = true;
   return CG_OK;
 }

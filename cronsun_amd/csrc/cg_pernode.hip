@@ -756,9 +756,9 @@ int per_node_locked(cg_ctx* c, const cg_specs* s, const cg_zone* z, int64_t t0, 
     HIPCHK(hipMemsetAsync(w.tickets.p, 0, kTicketGroups * kTicketStride * 4, st));
     (void)hipEventRecord(c->pev[2], st);
   }
-  (void)hipEventElapsedTime(&c->kt[6], c->pev[0], c->pev[1]);
-  (void)hipEventElapsedTime(&c->kt[7], c->pev[1], c->pev[2]);
-  (void)hipEventElapsedTime(&c->kt[8], c->pev[2], c->pev[3]);
+  (void)hipEventElapsedTime(&c->kt[KT_PN_JOIN], c->pev[0], c->pev[1]);
+  (void)hipEventElapsedTime(&c->kt[KT_PN_TRANSPOSE], c->pev[1], c->pev[2]);
+  (void)hipEventElapsedTime(&c->kt[KT_PN_WRITE], c->pev[2], c->pev[3]);
   c->pn_E = En;
   c->pn_valid = true;
   c->pn_nnz = nnz;
@@ -780,7 +780,7 @@ int per_node_locked(cg_ctx* c, const cg_specs* s, const cg_zone* z, int64_t t0, 
     }
     return rc;
   }
-  c->kt[12] = 0.f;
+  c->kt[KT_TIME_ORDER] = 0.f;
   return CG_OK;
 }
 
@@ -959,7 +959,7 @@ int cg_expand_per_node_wait(cg_ctx* c, int64_t* n_events, int64_t* n_events_all)
   HIPCHK(hipSetDevice(c->device));
   int rc = pn_async_drain(c);
   if (rc) return rc;
-  if (c->nw_n > 0) c->kt[8] = float(c->nw_ms_sum / c->nw_n);  // mean per-node writer time of the calls checked
+  if (c->nw_n > 0) c->kt[KT_PN_WRITE] = float(c->nw_ms_sum / c->nw_n);  // mean per-node writer time of the calls checked
   c->nw_ms_sum = 0;
   c->nw_n = 0;
   const int rc_async = c->pa_rc;

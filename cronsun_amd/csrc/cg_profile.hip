@@ -23,31 +23,22 @@
 //                     its walked fires touch (inflight_walk_row)
 //   k_node_peaks      one wave per node row: (max cell, first bucket with it)
 //
-// Admission profile (cg_admit_*): the fires Job.limit() would admit, or those it
-// would drop.  The start profile's first two kernels fill the rule matrix, then
-//   k_admit_prepare   one lane per cell: zeroes the rows the kind rewrites
-//                     (ADMITTED: of units that can drop; DROPPED: of the others)
-//   k_admit_units     one lane per unit that can drop: walks the unit's
-//                     admitted fires (cg_admit.h, admit_walk_unit) and adds
-//                     (ADMITTED) or subtracts (DROPPED) 1 in the rule's own row
-// and totals, node matrix and accessors are shared.
-//
-// Lock profile (cg_lock_profile_*): the fires the KindAlone / KindInterval
-// lock of Cmd.Run would grant, or those it would skip.  The admission chain
-// with the unit walk replaced:
-//   k_admit_prepare   flag = contending rule of a lock unit (GRANTED: those
-//                     rows restart from zero; SKIPPED: all other rows are zero)
-//   k_lock_units      one lane per lock unit with a contending rule: walks the
-//                     unit's granted fires (cg_lock.h, lock_walk_unit) and adds
-//                     (GRANTED) or subtracts (SKIPPED) 1 in the rule's own row
-//
+// Admission profile (cg_admit_*: the fires Job.limit() would admit, or those it
+// would drop) and lock profile (cg_lock_profile_*: the fires the KindAlone /
+// KindInterval lock of Cmd.Run would grant, or skip).  The start profile's
+// first two kernels fill the rule matrix, then a unit walk rewrites rows
+// (kernel side cg_unit_walk.h, host side cg_units.h); the rest is shared.
+//   k_admit_prepare   one lane per cell: zeroes the flagged rows -- of units
+//                     that can drop / contending rules of lock units -- when
+//                     the kind counts up (ADMITTED, GRANTED), else the others
+//   k_admit_units     one lane per unit that can drop: adds (ADMITTED) or
+//                     subtracts (DROPPED) 1 per admitted fire in the rule's row
+//   k_lock_units      one lane per lock unit with a contending rule: the same
+//                     per granted fire (GRANTED / SKIPPED)
 // Running profile (CG_PROFILE_RUNNING / CG_PROFILE_LOCK_RUNNING): commands in
 // flight counting only the fires that start.  The in-flight chain's first two
-// kernels fill the rule matrix with every rule's d, then
-//   k_admit_prepare   zeroes the flagged rows
-//   k_admit_units / k_lock_units  in difference mode: +1 at the bucket a started
-//                     fire comes into flight, -1 where it has ended
-//                     (cg_profile.h, running_emit_diff)
+// kernels, k_admit_prepare zeroing the flagged rows, the unit walk in
+// difference mode (cg_profile.h, running_emit_diff), then
 //   k_rows_prefix     in-place inclusive prefix sum along each flagged row
 #include <hip/hip_runtime.h>
 
@@ -57,10 +48,8 @@
 
 #include "../../include/cronsun_gpu.h"
 #include "cg_api_internal.h"
-#include "cg_admit.h"
-#include "cg_lock.h"
 #include "cg_profile.h"
-#include "cg_stage.h"
+#include "cg_unit_walk.h"
 #include "cg_units.h"
 
 using namespace cg;
@@ -72,8 +61,6 @@ constexpr int kMaxBuckets = 4096;
 // rows of the rule matrix (k_profile_totals) summed by one block per bucket tile
 constexpr int kTotalChunk = 4096;
 static_assert(kAdmitMaxParallels == CG_ADMIT_MAX_PARALLELS, "cg_admit.h and the public header disagree");
-static_assert(sizeof(AdmitUnit) == 24, "AdmitUnit is uploaded as 24-byte records");
-static_assert(sizeof(LockUnit) == 32, "LockUnit is uploaded as 32-byte records");
 static_assert(JOB_COMMON == CG_JOB_COMMON && JOB_ALONE == CG_JOB_ALONE && JOB_INTERVAL == CG_JOB_INTERVAL,
               "cg_time.h and the public header disagree");
 
@@ -210,58 +197,44 @@ __global__ __launch_bounds__(256) void k_admit_prepare(const uint8_t* __restrict
     if ((flag[i / B] != 0) == (zero_flagged != 0)) out[i] = 0;
 }
 
-// One lane per unit that can drop (units [U], compacted by the host so waves
-// are dense); a block is one wave.  The lane walks the unit's admitted fires
-// and adds `step` (+1 ADMITTED, -1 DROPPED: start - admitted) to the cell of
-// the firing rule's row -- rows belong to one unit, so plain read-modify-write.
-// With diff != 0 (RUNNING) it writes the fire's difference over its run time
-// u.d instead (cg_profile.h, running_emit_diff) and step is not read.
-// The ring of the last P admitted starts and the walked runs' remembered
-// positions (cg_admit.h) live in LDS behind the staged plan, [slot][lane]: a
-// lane's slots are 512 B (256 B) apart, conflict-free at any head.
-constexpr int kAdmitBlock = 64;
-__global__ __launch_bounds__(kAdmitBlock) void k_admit_units(const DSpec* __restrict__ specs, PlanArgs p,
-                                                              const int64_t* __restrict__ run_anchor,
-                                                              const int32_t* __restrict__ run_count,
-                                                              const uint32_t* __restrict__ run_dmask,
-                                                              const AdmitUnit* __restrict__ units, int64_t U,
-                                                              size_t ring_off, int64_t w, int32_t B, int32_t step,
-                                                              int32_t diff, int32_t* __restrict__ out) {
-  extern __shared__ __align__(16) char lds[];
-  PlanView v = stage_plan(p, lds);
-  // [ring 16][walk t 8] i64, then [rel 8][s 8][q 8] i32, each [slot][lane]
-  int64_t* ring = reinterpret_cast<int64_t*>(lds + ring_off) + threadIdx.x;
-  int32_t* w32 = reinterpret_cast<int32_t*>(ring - threadIdx.x + (kAdmitMaxParallels + kAdmitWalkSlots) * kAdmitBlock) +
-                 threadIdx.x;
-  const AdmitWalkCache wc{ring + kAdmitMaxParallels * kAdmitBlock, w32, w32 + kAdmitWalkSlots * kAdmitBlock,
-                          w32 + 2 * kAdmitWalkSlots * kAdmitBlock, kAdmitBlock};
-  const int64_t i = blockIdx.x * int64_t(kAdmitBlock) + threadIdx.x;
-  if (i >= U) return;
-  const AdmitUnit u = units[i];
-  const int64_t t0 = p.t0;
-  admit_walk_unit(specs, v.z, v.segs, p.G, run_anchor, run_count, run_dmask, t0, p.t1, u, ring, kAdmitBlock, wc,
-                  [&](int64_t r, int64_t t) {
-                    if (diff) {  // RUNNING: the fire's difference, summed by k_rows_prefix
-                      running_emit_diff(out + r * B, B, t, u.d, t0, w);
-                      return;
-                    }
-                    const int64_t b = (t - t0 - 1) / w;
-                    if (t > t0 && b < B) out[r * B + b] += step;
-                  });
+// A unit kernel's fire t of rule r (d: the unit's run time): `step` added to the
+// cell of the rule's own row (a row belongs to one unit: plain read-modify-write)
+// or, with diff != 0 (RUNNING kinds), the fire's difference over d
+// (cg_profile.h, running_emit_diff; step is not read), which k_rows_prefix sums.
+struct ProfileEmit {
+  int64_t t0, w;
+  int32_t B, step, diff;
+  int32_t* out;
+  __device__ __forceinline__ void operator()(int64_t r, int64_t t, int64_t d) const {
+    if (diff) {
+      running_emit_diff(out + r * B, B, t, d, t0, w);
+      return;
+    }
+    const int64_t b = (t - t0 - 1) / w;
+    if (t > t0 && b < B) out[r * B + b] += step;
+  }
+};
+
+// One lane per unit that can drop (units [U], compacted by the host so waves are
+// dense; cg_unit_walk.h).  step: +1 ADMITTED, -1 DROPPED (start - admitted).
+__global__ __launch_bounds__(kUnitBlock) void k_admit_units(const DSpec* __restrict__ specs, PlanArgs p,
+                                                             const int64_t* __restrict__ run_anchor,
+                                                             const int32_t* __restrict__ run_count,
+                                                             const uint32_t* __restrict__ run_dmask,
+                                                             const AdmitUnit* __restrict__ units, int64_t U,
+                                                             size_t ring_off, int64_t w, int32_t B, int32_t step,
+                                                             int32_t diff, int32_t* __restrict__ out) {
+  const ProfileEmit e{p.t0, w, B, step, diff, out};
+  admit_unit_lane(specs, p, run_anchor, run_count, run_dmask, units, U, ring_off,
+                  [&](const PlanView&, const AdmitUnit& u, int64_t r, int64_t t) { e(r, t, u.d); });
 }
 
 // ----------------------------------------------------------- lock profile --
-// One lane per lock unit with a contending rule (units [U], compacted by the
-// host so waves are dense); a block is one wave.  The lane walks the unit's
-// granted fires and adds `step` (+1 GRANTED, -1 SKIPPED: start - granted) to
-// the cell of the firing rule's row -- a row belongs to one unit, so plain
-// read-modify-write.  With diff != 0 (LOCK_RUNNING) it writes the fire's
-// difference over u.d instead, as k_admit_units does.  contends [R]: the prepare pass's flags, inside a lock
-// unit "this rule reaches the lock".  The walked runs' remembered positions
-// (cg_admit.h) live in LDS behind the staged plan, [slot][lane]; there is no
-// ring.  A rule whose Next never returns lowers *stuck to its index.
-constexpr int kLockBlock = 64;
-__global__ __launch_bounds__(kLockBlock) void k_lock_units(const DSpec* __restrict__ specs, PlanArgs p,
+// One lane per lock unit with a contending rule.  step: +1 GRANTED, -1 SKIPPED
+// (start - granted); in difference mode the command runs u.d whatever its lease
+// does.  contends [R]: the prepare pass's flags, inside a lock unit "this rule
+// reaches the lock".  A rule whose Next never returns lowers *stuck to its index.
+__global__ __launch_bounds__(kUnitBlock) void k_lock_units(const DSpec* __restrict__ specs, PlanArgs p,
                                                             const int64_t* __restrict__ run_anchor,
                                                             const int32_t* __restrict__ run_count,
                                                             const uint32_t* __restrict__ run_dmask,
@@ -270,26 +243,10 @@ __global__ __launch_bounds__(kLockBlock) void k_lock_units(const DSpec* __restri
                                                             int64_t lock_ttl, int64_t w, int32_t B, int32_t step,
                                                             int32_t diff, int32_t* __restrict__ out,
                                                             unsigned long long* __restrict__ stuck) {
-  extern __shared__ __align__(16) char lds[];
-  PlanView v = stage_plan(p, lds);
-  // [walk t 8] i64, then [rel 8][s 8][q 8] i32, each [slot][lane]
-  int64_t* wt = reinterpret_cast<int64_t*>(lds + cache_off) + threadIdx.x;
-  int32_t* w32 = reinterpret_cast<int32_t*>(lds + cache_off + size_t(kAdmitWalkSlots) * kLockBlock * 8) + threadIdx.x;
-  const AdmitWalkCache wc{wt, w32, w32 + kAdmitWalkSlots * kLockBlock, w32 + 2 * kAdmitWalkSlots * kLockBlock,
-                          kLockBlock};
-  const int64_t i = blockIdx.x * int64_t(kLockBlock) + threadIdx.x;
-  if (i >= U) return;
-  const LockUnit u = units[i];
-  const int64_t t0 = p.t0;
-  const int64_t bad = lock_walk_unit(specs, v.z, v.segs, p.G, run_anchor, run_count, run_dmask, t0, p.t1, u, lock_ttl,
-                                     contends, wc, [&](int64_t r, int64_t t) {
-                                       if (diff) {  // LOCK_RUNNING: the command runs u.d whatever its lease does
-                                         running_emit_diff(out + r * B, B, t, u.d, t0, w);
-                                         return;
-                                       }
-                                       const int64_t b = (t - t0 - 1) / w;
-                                       if (t > t0 && b < B) out[r * B + b] += step;
-                                     });
+  const ProfileEmit e{p.t0, w, B, step, diff, out};
+  const int64_t bad =
+      lock_unit_lane(specs, p, run_anchor, run_count, run_dmask, units, U, cache_off, contends, lock_ttl,
+                     [&](const PlanView&, const LockUnit& u, int64_t r, int64_t t) { e(r, t, u.d); });
   if (bad >= 0) atomicMin(stuck, static_cast<unsigned long long>(bad));
 }
 
@@ -510,170 +467,166 @@ int profile_check_args(const char* what, const cg_ctx* c, const cg_specs* s, con
   return CG_OK;
 }
 
-int ensure_events(cg_ctx* c) {
-  for (hipEvent_t& e : c->pfev)
-    if (!e) HIPCHK(hipEventCreateWithFlags(&e, hipEventDisableSystemFence));
+// What a profile call computes, built by its entry point: the kind, the
+// in-flight durations (host, [R], whole seconds clamped to B * w; null: the base
+// rows are the start profile's) and an admission or a lock call's checked
+// arguments (cg_units.h; at most one).  A RUNNING kind has both.
+struct ProfileCall {
+  int kind = CG_PROFILE_STARTS;
+  const std::vector<int64_t>* dsec = nullptr;
+  const AdmitCall* adm = nullptr;
+  const LockCall* lk = nullptr;
+  static ProfileCall inflight(const std::vector<int64_t>* d) { return {CG_PROFILE_INFLIGHT, d, nullptr, nullptr}; }
+  static ProfileCall admission(const AdmitCall* a) { return {a->what, a->durations(), a, nullptr}; }
+  static ProfileCall lock(const LockCall* l) { return {l->what, l->durations(), nullptr, l}; }
+  bool has_unit_walk() const { return adm || lk; }
+  bool running() const { return kind == CG_PROFILE_RUNNING || kind == CG_PROFILE_LOCK_RUNNING; }
+  int64_t units() const { return int64_t(adm ? adm->units.size() : lk ? lk->units.size() : 0); }
+  // k_admit_prepare zeroes the flagged rows (else the others); the walk adds (else subtracts)
+  bool counts_up() const { return kind != CG_PROFILE_DROPPED && kind != CG_PROFILE_LOCK_SKIPPED; }
+};
+
+// the event the unit walk ends at (every call records it, with or without a walk)
+hipEvent_t walk_end_event(cg_ctx* c, bool running) { return c->pfev[running ? PFEV_PREFIX : PFEV_TOTALS]; }
+
+// base rows: the start profile's or, with durations, the in-flight profile's
+int profile_base_rows(cg_ctx* c, const cg_specs* s, int64_t w, int32_t B, const ProfileCall& pc) {
+  RunSet& rs = c->rs;
+  hipStream_t st = c->st;
+  const int64_t R = int64_t(s->n);
+  const size_t lds = plan_lds_bytes(rs.pa);
+  if (pc.dsec) {
+    // (*dsec outlives the stream synchronise that ends the call)
+    if (int rc = c->pf_dur.ensure(size_t(R))) return rc;
+    HIPCHK(hipMemcpyAsync(c->pf_dur.p, pc.dsec->data(), size_t(R) * 8, hipMemcpyHostToDevice, st));
+  }
+  // either flavour's kernel of a step: the in-flight one also takes the durations
+  const auto launch = [&](auto starts, auto inflight, int blocks) {
+    if (pc.dsec)
+      hipLaunchKernelGGL(inflight, dim3(blocks), dim3(256), lds, st, s->d, R, rs.pa, rs.run_anchor.p, rs.run_count.p,
+                         rs.run_dmask.p, c->pf_dur.p, w, B, c->pf_rules.p);
+    else
+      hipLaunchKernelGGL(starts, dim3(blocks), dim3(256), lds, st, s->d, R, rs.pa, rs.run_anchor.p, rs.run_count.p,
+                         rs.run_dmask.p, w, B, c->pf_rules.p);
+  };
+  (void)hipEventRecord(c->pfev[PFEV_RULES], st);
+  launch(k_profile_rules, k_inflight_rules, gridn(R * B, 256, 4096));
+  (void)hipEventRecord(c->pfev[PFEV_WALK], st);
+  if (rs.has_walk()) launch(k_profile_walk, k_inflight_walk, gridn(R, 256, 256 * 16));
   return CG_OK;
 }
 
-// count chain + rule matrix + totals, enqueued on the ctx stream (the caller
-// drains it); c->mu held.  pfev[0..3] bracket the three kernels (pfev[3]:
-// the end of the totals, where a per-node call's join starts).  dsec: null for
-// the start profile, else the in-flight profile's durations (host, [R], whole
-// seconds clamped to B * w), uploaded here and read by this call's kernels only;
-// it comes together with adm or lk in a RUNNING call, whose base rows are the
-// in-flight profile's and whose unit walk writes differences that k_rows_prefix
-// sums (pfev[8]: the end of that walk; pfev[2] then follows the prefix).
-// adm / lk: an admission or a lock call's checked arguments (cg_units.h).
+// the base rows are in place: an admission or a lock call rewrites them on the
+// same stream.  A lock call then drains the stream to learn of a stuck rule.
+int profile_unit_rewrite(cg_ctx* c, const cg_specs* s, int64_t w, int32_t B, const ProfileCall& pc) {
+  RunSet& rs = c->rs;
+  hipStream_t st = c->st;
+  const int64_t R = int64_t(s->n), U = pc.units();
+  const size_t lds = plan_lds_bytes(rs.pa), tail_off = unit_tail_off(lds);
+  const int32_t step = pc.counts_up() ? 1 : -1, diff = pc.running() ? 1 : 0;
+  const unsigned blocks = unsigned((U + kUnitBlock - 1) / kUnitBlock);
+  if (int rc = unit_upload(c, R, pc.adm, pc.lk, nullptr, pc.lk != nullptr)) return rc;
+  const uint8_t* flag = c->uw_flag[pc.lk ? 1 : 0].p;
+  (void)hipEventRecord(c->pfev[PFEV_PREPARE], st);
+  hipLaunchKernelGGL(k_admit_prepare, dim3(gridn(R * B, 256, 4096)), dim3(256), 0, st, flag, R, B,
+                     pc.counts_up() ? 1 : 0, c->pf_rules.p);
+  (void)hipEventRecord(c->pfev[PFEV_UNITS], st);
+  if (U > 0 && pc.adm)
+    hipLaunchKernelGGL(k_admit_units, dim3(blocks), dim3(kUnitBlock), admit_lds_bytes(lds), st, s->d, rs.pa,
+                       rs.run_anchor.p, rs.run_count.p, rs.run_dmask.p, uw_admit_units(c), U, tail_off, w, B, step,
+                       diff, c->pf_rules.p);
+  if (U > 0 && pc.lk)
+    hipLaunchKernelGGL(k_lock_units, dim3(blocks), dim3(kUnitBlock), lock_lds_bytes(lds), st, s->d, rs.pa,
+                       rs.run_anchor.p, rs.run_count.p, rs.run_dmask.p, uw_lock_units(c), U, flag, tail_off,
+                       pc.lk->lock_ttl, w, B, step, diff, c->pf_rules.p, c->uw_err.p + 1);
+  (void)hipEventRecord(walk_end_event(c, pc.running()), st);
+  if (!pc.lk) return CG_OK;
+  HIPCHK(hipGetLastError());
+  unsigned long long err[2];
+  if (int rc = unit_errors(c, err)) return rc;
+  if (err[1] != ~0ULL) return cg_fail(CG_ERANGE, lock_stuck_msg("cg_lock_profile", err[1]));  // no profile
+  return CG_OK;
+}
+
+// a RUNNING call's flagged rows hold differences: summed along the buckets (no
+// unit to walk: no row is flagged); then the column totals of any kind
+int profile_prefix_totals(cg_ctx* c, int64_t R, int32_t B, const ProfileCall& pc) {
+  hipStream_t st = c->st;
+  if (pc.running()) {
+    if (pc.units() > 0)
+      hipLaunchKernelGGL(k_rows_prefix, dim3(gridn(R, B >= 64 ? 4 : 4 * (64 / B), 4096)), dim3(256), 0, st,
+                         c->uw_flag[pc.lk ? 1 : 0].p, R, B, c->pf_rules.p);
+    (void)hipEventRecord(c->pfev[PFEV_TOTALS], st);
+  }
+  hipLaunchKernelGGL(k_profile_totals, dim3(gridn(R, kTotalChunk, 1 << 30), (B + 63) / 64), dim3(256), 0, st,
+                     c->pf_rules.p, R, B, reinterpret_cast<unsigned long long*>(c->pf_totals.p));
+  (void)hipEventRecord(c->pfev[PFEV_TOTALS_END], st);
+  HIPCHK(hipGetLastError());
+  return CG_OK;
+}
+
+// count chain + rule matrix + totals, enqueued on the ctx stream (the caller drains it); c->mu
+// held.  Every event is recorded once up front, so the slots of a phase that does not run read 0.
 int profile_rules_enqueue(cg_ctx* c, const cg_specs* s, const cg_zone* z, int64_t t0, int64_t w, int32_t B,
-                          const std::vector<int64_t>* dsec, const AdmitCall* adm = nullptr,
-                          const LockCall* lk = nullptr) {
+                          const ProfileCall& pc) {
   c->pf_valid = false;
   c->pf_has_nodes = false;
   c->pf_peaks_valid = false;
   c->tr_valid = false;  // a top-rules result does not outlive its profile
   int rc;
   bool empty = true;
-  if ((rc = sync_count_scan(c, s, z, t0, t0 + int64_t(B) * w, &empty, 0, lk != nullptr))) return rc;
-  if ((rc = ensure_events(c))) return rc;
+  if ((rc = sync_count_scan(c, s, z, t0, t0 + int64_t(B) * w, &empty, 0, pc.lk != nullptr))) return rc;
+  if ((rc = ensure_events(c->pfev))) return rc;
   const int64_t R = int64_t(s->n);
   if ((rc = c->pf_rules.ensure(size_t(std::max<int64_t>(R * B, 1)))) || (rc = c->pf_totals.ensure(size_t(B))))
     return rc;
   hipStream_t st = c->st;
   HIPCHK(hipMemsetAsync(c->pf_totals.p, 0, size_t(B) * 8, st));
-  for (int i = 14; i < 23; i++) c->kt[i] = 0.f;
-  const bool running = (adm && adm->running()) || (lk && lk->running());
-  hipEvent_t walk_end = c->pfev[running ? 8 : 2];
-  for (int i : {0, 1, 6, 7}) (void)hipEventRecord(c->pfev[i], st);
-  if (running) (void)hipEventRecord(walk_end, st);
-  for (int i : {2, 3}) (void)hipEventRecord(c->pfev[i], st);
+  for (int i = KT_PF_RULES; i < KT_COUNT; i++) c->kt[i] = 0.f;
+  for (int i : {PFEV_RULES, PFEV_WALK, PFEV_PREPARE, PFEV_UNITS}) (void)hipEventRecord(c->pfev[i], st);
+  if (pc.running()) (void)hipEventRecord(c->pfev[PFEV_PREFIX], st);
+  for (int i : {PFEV_TOTALS, PFEV_TOTALS_END}) (void)hipEventRecord(c->pfev[i], st);
   if (!empty) {
-    RunSet& rs = c->rs;
     // a rule whose reference loop never ends: refuse before any cell is computed
     HIPCHK(hipStreamSynchronize(st));
-    const unsigned long long stuck = static_cast<unsigned long long>(rs.res_host[1]);
+    const unsigned long long stuck = static_cast<unsigned long long>(c->rs.res_host[1]);
     if (stuck != ~0ULL) return cg_fail(CG_ERANGE, stuck_msg(stuck));
-    const size_t lds = plan_lds_bytes(rs.pa);
-    const size_t cache_off = align_up(lds, 16), lock_lds = cache_off + size_t(kLockBlock) * kLockLaneBytes;
-    if (lk && !lk->units.empty() && lock_lds > 64 * 1024)
-      return cg_fail(CG_ERANGE, "cg_lock_profile: the plan of this horizon leaves no LDS for the walked runs' positions");
-    if (dsec) {
-      // (*dsec outlives the stream synchronise that ends the call)
-      if ((rc = c->pf_dur.ensure(size_t(R)))) return rc;
-      HIPCHK(hipMemcpyAsync(c->pf_dur.p, dsec->data(), size_t(R) * 8, hipMemcpyHostToDevice, st));
-    }
-    (void)hipEventRecord(c->pfev[0], st);
-    if (dsec)
-      hipLaunchKernelGGL(k_inflight_rules, dim3(gridn(R * B, 256, 4096)), dim3(256), lds, st, s->d, R, rs.pa,
-                         rs.run_anchor.p, rs.run_count.p, rs.run_dmask.p, c->pf_dur.p, w, B, c->pf_rules.p);
-    else
-      hipLaunchKernelGGL(k_profile_rules, dim3(gridn(R * B, 256, 4096)), dim3(256), lds, st, s->d, R, rs.pa,
-                         rs.run_anchor.p, rs.run_count.p, rs.run_dmask.p, w, B, c->pf_rules.p);
-    (void)hipEventRecord(c->pfev[1], st);
-    if (rs.has_walk()) {
-      if (dsec)
-        hipLaunchKernelGGL(k_inflight_walk, dim3(gridn(R, 256, 256 * 16)), dim3(256), lds, st, s->d, R, rs.pa,
-                           rs.run_anchor.p, rs.run_count.p, rs.run_dmask.p, c->pf_dur.p, w, B, c->pf_rules.p);
-      else
-        hipLaunchKernelGGL(k_profile_walk, dim3(gridn(R, 256, 256 * 16)), dim3(256), lds, st, s->d, R, rs.pa,
-                           rs.run_anchor.p, rs.run_count.p, rs.run_dmask.p, w, B, c->pf_rules.p);
-    }
-    if (adm) {
-      // the start rows are in place: rewrite them on the same stream
-      const int64_t U = int64_t(adm->units.size());
-      const size_t ring_off = align_up(lds, 16), admit_lds = ring_off + size_t(kAdmitBlock) * kAdmitLaneBytes;
-      if (U > 0 && admit_lds > 64 * 1024) return cg_fail(CG_ERANGE, "cg_admit: the plan of this horizon leaves no LDS for the admission ring");
-      if ((rc = c->pf_admit_flag.ensure(size_t(R))) || (rc = c->pf_admit_units.ensure(size_t(std::max<int64_t>(U, 1)) * sizeof(AdmitUnit))))
-        return rc;
-      HIPCHK(hipMemcpyAsync(c->pf_admit_flag.p, adm->flag.data(), size_t(R), hipMemcpyHostToDevice, st));
-      if (U > 0)
-        HIPCHK(hipMemcpyAsync(c->pf_admit_units.p, adm->units.data(), size_t(U) * sizeof(AdmitUnit), hipMemcpyHostToDevice, st));
-      (void)hipEventRecord(c->pfev[6], st);
-      hipLaunchKernelGGL(k_admit_prepare, dim3(gridn(R * B, 256, 4096)), dim3(256), 0, st, c->pf_admit_flag.p, R, B,
-                         adm->what != CG_PROFILE_DROPPED ? 1 : 0, c->pf_rules.p);
-      (void)hipEventRecord(c->pfev[7], st);
-      if (U > 0)
-        hipLaunchKernelGGL(k_admit_units, dim3(unsigned((U + kAdmitBlock - 1) / kAdmitBlock)), dim3(kAdmitBlock), admit_lds,
-                           st, s->d, rs.pa, rs.run_anchor.p, rs.run_count.p, rs.run_dmask.p,
-                           reinterpret_cast<const AdmitUnit*>(c->pf_admit_units.p), U, ring_off, w, B,
-                           adm->what == CG_PROFILE_DROPPED ? -1 : 1, running ? 1 : 0, c->pf_rules.p);
-    }
-    if (lk) {
-      const int64_t U = int64_t(lk->units.size());
-      if ((rc = c->pf_admit_flag.ensure(size_t(R))) ||
-          (rc = c->pf_admit_units.ensure(size_t(std::max<int64_t>(U, 1)) * sizeof(LockUnit))) ||
-          (rc = c->pf_lock_stuck.ensure(1)))
-        return rc;
-      HIPCHK(hipMemcpyAsync(c->pf_admit_flag.p, lk->flag.data(), size_t(R), hipMemcpyHostToDevice, st));
-      if (U > 0)
-        HIPCHK(hipMemcpyAsync(c->pf_admit_units.p, lk->units.data(), size_t(U) * sizeof(LockUnit), hipMemcpyHostToDevice, st));
-      HIPCHK(hipMemsetAsync(c->pf_lock_stuck.p, 0xFF, sizeof(unsigned long long), st));
-      (void)hipEventRecord(c->pfev[6], st);
-      hipLaunchKernelGGL(k_admit_prepare, dim3(gridn(R * B, 256, 4096)), dim3(256), 0, st, c->pf_admit_flag.p, R, B,
-                         lk->what != CG_PROFILE_LOCK_SKIPPED ? 1 : 0, c->pf_rules.p);
-      (void)hipEventRecord(c->pfev[7], st);
-      if (U > 0)
-        hipLaunchKernelGGL(k_lock_units, dim3(unsigned((U + kLockBlock - 1) / kLockBlock)), dim3(kLockBlock), lock_lds, st,
-                           s->d, rs.pa, rs.run_anchor.p, rs.run_count.p, rs.run_dmask.p,
-                           reinterpret_cast<const LockUnit*>(c->pf_admit_units.p), U, c->pf_admit_flag.p, cache_off,
-                           lk->lock_ttl, w, B, lk->what == CG_PROFILE_LOCK_SKIPPED ? -1 : 1, running ? 1 : 0,
-                           c->pf_rules.p, c->pf_lock_stuck.p);
-      (void)hipEventRecord(walk_end, st);
-      HIPCHK(hipGetLastError());
-      // a granted fire whose Next never returns: the reference hangs in
-      // lockTtl there, and the unit's rows are unfinished -- no profile
-      unsigned long long lstuck = ~0ULL;
-      HIPCHK(hipMemcpyAsync(&lstuck, c->pf_lock_stuck.p, sizeof lstuck, hipMemcpyDeviceToHost, st));
-      HIPCHK(hipStreamSynchronize(st));
-      if (lstuck != ~0ULL)
-        return cg_fail(CG_ERANGE, "cg_lock_profile: rule " + std::to_string(lstuck) +
-                                      ": Next never returns from a fire of this horizon that finds the lock free "
-                                      "(the reference's lockTtl does not return there)");
+    const size_t lds = plan_lds_bytes(c->rs.pa);
+    if (pc.units() > 0 && (rc = pc.adm ? admit_lds_check("cg_admit", lds) : lock_lds_check("cg_lock_profile", lds)))
+      return rc;
+    if ((rc = profile_base_rows(c, s, w, B, pc))) return rc;
+    if (pc.has_unit_walk()) {
+      if ((rc = profile_unit_rewrite(c, s, w, B, pc))) return rc;
     } else {
-      (void)hipEventRecord(walk_end, st);
+      (void)hipEventRecord(walk_end_event(c, false), st);
     }
-    if (running) {
-      // the flagged rows hold differences: sum them along the buckets (rows of
-      // a call without a unit to walk are all unflagged)
-      const int rows_per_block = B >= 64 ? 4 : 4 * (64 / B);
-      if ((adm ? adm->units.size() : lk->units.size()) > 0)
-        hipLaunchKernelGGL(k_rows_prefix, dim3(gridn(R, rows_per_block, 4096)), dim3(256), 0, st, c->pf_admit_flag.p, R,
-                           B, c->pf_rules.p);
-      (void)hipEventRecord(c->pfev[2], st);
-    }
-    hipLaunchKernelGGL(k_profile_totals, dim3(gridn(R, kTotalChunk, 1 << 30), (B + 63) / 64), dim3(256), 0, st,
-                       c->pf_rules.p, R, B, reinterpret_cast<unsigned long long*>(c->pf_totals.p));
-    (void)hipEventRecord(c->pfev[3], st);
-    HIPCHK(hipGetLastError());
+    if ((rc = profile_prefix_totals(c, R, B, pc))) return rc;
   }
   c->pf_R = R;
   c->pf_B = B;
   c->pf_N = 0;
-  c->pf_kind = lk ? lk->what : adm ? adm->what : dsec ? CG_PROFILE_INFLIGHT : CG_PROFILE_STARTS;
+  c->pf_kind = pc.kind;
   return CG_OK;
 }
 
 void profile_rule_times(cg_ctx* c) {
-  for (int i = 0; i < 3; i++) (void)hipEventElapsedTime(&c->kt[14 + i], c->pfev[i], c->pfev[i + 1]);
-  const bool running = c->pf_kind == CG_PROFILE_RUNNING || c->pf_kind == CG_PROFILE_LOCK_RUNNING;
-  hipEvent_t walk_end = c->pfev[running ? 8 : 2];
-  if (c->pf_kind == CG_PROFILE_ADMITTED || c->pf_kind == CG_PROFILE_DROPPED || c->pf_kind == CG_PROFILE_RUNNING) {
-    // the admission kernels sit between the walked runs and the totals
-    (void)hipEventElapsedTime(&c->kt[15], c->pfev[1], c->pfev[6]);
-    (void)hipEventElapsedTime(&c->kt[19], c->pfev[6], c->pfev[7]);
-    (void)hipEventElapsedTime(&c->kt[20], c->pfev[7], walk_end);
+  const auto ms = [c](Kt slot, int from, hipEvent_t to) { (void)hipEventElapsedTime(&c->kt[slot], c->pfev[from], to); };
+  const int k = c->pf_kind;
+  const bool running = k == CG_PROFILE_RUNNING || k == CG_PROFILE_LOCK_RUNNING;
+  const bool admission = k == CG_PROFILE_ADMITTED || k == CG_PROFILE_DROPPED || k == CG_PROFILE_RUNNING;
+  const bool lock = k == CG_PROFILE_LOCK_GRANTED || k == CG_PROFILE_LOCK_SKIPPED || k == CG_PROFILE_LOCK_RUNNING;
+  ms(KT_PF_RULES, PFEV_RULES, c->pfev[PFEV_WALK]);
+  ms(KT_PF_WALK, PFEV_WALK, c->pfev[admission || lock ? PFEV_PREPARE : PFEV_TOTALS]);
+  ms(KT_PF_TOTALS, PFEV_TOTALS, c->pfev[PFEV_TOTALS_END]);
+  if (admission || lock) {  // the unit kernels sit between the walked runs and the totals
+    ms(KT_UNIT_PREPARE, PFEV_PREPARE, c->pfev[PFEV_UNITS]);
+    ms(admission ? KT_ADMIT_UNITS : KT_LOCK_UNITS, PFEV_UNITS, walk_end_event(c, running));
   }
-  if (c->pf_kind == CG_PROFILE_LOCK_GRANTED || c->pf_kind == CG_PROFILE_LOCK_SKIPPED ||
-      c->pf_kind == CG_PROFILE_LOCK_RUNNING) {
-    (void)hipEventElapsedTime(&c->kt[15], c->pfev[1], c->pfev[6]);
-    (void)hipEventElapsedTime(&c->kt[19], c->pfev[6], c->pfev[7]);
-    (void)hipEventElapsedTime(&c->kt[21], c->pfev[7], walk_end);
-  }
-  if (running) (void)hipEventElapsedTime(&c->kt[22], c->pfev[8], c->pfev[2]);  // k_rows_prefix
-  // the count and scan behind it, when the chain recorded their events ([0], [1])
+  if (running) ms(KT_ROWS_PREFIX, PFEV_PREFIX, c->pfev[PFEV_TOTALS]);
+  // the count and scan behind it, when the chain recorded their events
   if (c->phase_timing >= 2 && c->pf_R > 0) {
-    (void)hipEventElapsedTime(&c->kt[0], c->ev[0], c->ev[1]);
-    (void)hipEventElapsedTime(&c->kt[1], c->ev[1], c->ev[2]);
+    (void)hipEventElapsedTime(&c->kt[KT_X_COUNT], c->ev[0], c->ev[1]);
+    (void)hipEventElapsedTime(&c->kt[KT_X_SCAN], c->ev[1], c->ev[2]);
   }
 }
 
@@ -694,49 +647,21 @@ int inflight_durations(const char* what, const cg_specs* s, const int64_t* dur_m
   return CG_OK;
 }
 
-// the rule-matrix call of either kind (dsec null: starts); arguments checked
-int profile_call(cg_ctx* c, const cg_specs* s, const cg_zone* z, int64_t t0, int64_t width, int32_t n_buckets,
-                 const std::vector<int64_t>* dsec, const AdmitCall* adm = nullptr, const LockCall* lk = nullptr) {
-  std::lock_guard<std::mutex> g(c->mu);
-  (void)hipGetLastError();  // clear a stale error so launch checks see only their own
-  int rc = profile_rules_enqueue(c, s, z, t0, width, n_buckets, dsec, adm, lk);
-  if (rc) return rc;
-  HIPCHK(hipStreamSynchronize(c->st));
-  profile_rule_times(c);
-  c->pf_valid = true;
-  return CG_OK;
-}
-
-int profile_check_node_args(const char* what, const cg_specs* s, const cg_rules* rules, int mode) {
-  if (!rules) return cg_fail(CG_EINVAL, std::string(what) + ": null");
-  if (mode < 0 || mode > 2) return cg_fail(CG_EINVAL, "bad exclude mode");
-  if (int64_t(s->n) != rules->st.n_rules) return cg_fail(CG_EINVAL, "specs count != rules n_rules");
-  return CG_OK;
-}
-
-// the per-node call of either kind; arguments checked
-int profile_per_node_call(cg_ctx* c, const cg_specs* s, const cg_zone* z, int64_t t0, int64_t width,
-                          int32_t n_buckets, const cg_rules* rules, int mode, const std::vector<int64_t>* dsec,
-                          const AdmitCall* adm = nullptr, const LockCall* lk = nullptr) {
-  const RulesStore& in = rules->st;
-  std::lock_guard<std::mutex> g(c->mu);
-  (void)hipGetLastError();
-  const int32_t B = n_buckets, N = in.n_nodes;
-  int rc = profile_rules_enqueue(c, s, z, t0, width, B, dsec, adm, lk);
-  if (rc) return rc;
+// the node matrix of the rule matrix just enqueued, behind it on the stream
+int profile_nodes_enqueue(cg_ctx* c, const RulesStore& in, int mode, int32_t B, bool cached, int64_t* nnz) {
   hipStream_t st = c->st;
+  const int32_t N = in.n_nodes;
+  int rc;
   // the rule->node join and its transpose: the per-node path's cache, keyed
   // by (rule set, exclude mode); rebuilt here on a miss (the cached segment
   // bounds go with the old transpose), its keys set once the stream drained
-  const bool cached = in.serial != 0 && in.serial == c->pn_cache_serial && mode == c->pn_cache_mode;
-  int64_t nnz = c->pn_nnz;
   if (!cached) {
     c->pn_cache_serial = 0;
     c->pn_K = 0;
-    if ((rc = rule_nodes_locked(c, in, mode, &nnz)) || (rc = transpose_locked(c, nnz, N))) return rc;
+    if ((rc = rule_nodes_locked(c, in, mode, nnz)) || (rc = transpose_locked(c, *nnz, N))) return rc;
   }
-  (void)hipEventRecord(c->pfev[4], st);
-  const int64_t chunks_max = int64_t(N) + nnz / kNodeChunk + 1;  // >= the chunk total
+  (void)hipEventRecord(c->pfev[PFEV_NODES], st);
+  const int64_t chunks_max = int64_t(N) + *nnz / kNodeChunk + 1;  // >= the chunk total
   if ((rc = c->pf_nodes.ensure(size_t(std::max<int64_t>(int64_t(N) * B, 1)))) ||
       (rc = c->pf_part.ensure(size_t(chunks_max * B))) || (rc = c->pf_chunk_cnt.ensure(size_t(std::max(N, 1)))) ||
       (rc = c->pf_chunk_off.ensure(size_t(N) + 1)) ||
@@ -751,22 +676,55 @@ int profile_per_node_call(cg_ctx* c, const cg_specs* s, const cg_zone* z, int64_
     hipLaunchKernelGGL(k_profile_nodes_reduce, dim3(gridn(int64_t(N) * B, 256, 1 << 30)), dim3(256), 0, st,
                        c->pf_chunk_off.p, N, B, c->pf_part.p, c->pf_nodes.p);
   }
-  (void)hipEventRecord(c->pfev[5], st);
+  (void)hipEventRecord(c->pfev[PFEV_NODES_END], st);
   HIPCHK(hipGetLastError());
-  HIPCHK(hipStreamSynchronize(st));
-  if (!cached) {
-    c->pn_nnz = nnz;
-    c->pn_cache_serial = in.serial;
-    c->pn_cache_mode = mode;
+  return CG_OK;
+}
+
+// A profile call of any kind, arguments checked; rules null: the flat flavour,
+// no node matrix.  Copies on the stream read the entry point's locals (durations,
+// units, flags): a call that fails before its synchronise drains the stream.
+int profile_call(cg_ctx* c, const cg_specs* s, const cg_zone* z, int64_t t0, int64_t width, int32_t B,
+                 const ProfileCall& pc, const cg_rules* rules, int mode) {
+  std::lock_guard<std::mutex> g(c->mu);
+  (void)hipGetLastError();  // clear a stale error so launch checks see only their own
+  const RulesStore* in = rules ? &rules->st : nullptr;
+  int64_t nnz = c->pn_nnz;
+  int rc = profile_rules_enqueue(c, s, z, t0, width, B, pc);
+  const bool cached = in && in->serial != 0 && in->serial == c->pn_cache_serial && mode == c->pn_cache_mode;
+  if (!rc && in) rc = profile_nodes_enqueue(c, *in, mode, B, cached, &nnz);
+  if (!rc) rc = cg_hip_check(hipStreamSynchronize(c->st), "hipStreamSynchronize(c->st)");
+  if (rc) {
+    (void)hipStreamSynchronize(c->st);
+    return rc;
   }
   profile_rule_times(c);
-  if (!cached) (void)hipEventElapsedTime(&c->kt[17], c->pfev[3], c->pfev[4]);  // 0: the cached join was reused
-  (void)hipEventElapsedTime(&c->kt[18], c->pfev[4], c->pfev[5]);
-  c->pf_N = N;
-  c->pf_nnz = nnz;
-  c->pf_nt_gen = c->nt_gen;  // the transpose the node matrix was summed from
-  c->pf_has_nodes = true;
+  if (in) {
+    if (!cached) {
+      c->pn_nnz = nnz;
+      c->pn_cache_serial = in->serial;
+      c->pn_cache_mode = mode;
+      (void)hipEventElapsedTime(&c->kt[KT_PF_JOIN], c->pfev[PFEV_TOTALS_END], c->pfev[PFEV_NODES]);
+    }
+    (void)hipEventElapsedTime(&c->kt[KT_PF_NODES], c->pfev[PFEV_NODES], c->pfev[PFEV_NODES_END]);
+    c->pf_N = in->n_nodes;
+    c->pf_nnz = nnz;
+    c->pf_nt_gen = c->nt_gen;  // the transpose the node matrix was summed from
+    c->pf_has_nodes = true;
+  }
   c->pf_valid = true;
+  return CG_OK;
+}
+
+// what the eight entry points check first: the bucket arguments, then a
+// per-node flavour's node arguments; the kind's own (durations / units) follow
+int profile_prelude(const char* fn, const cg_ctx* c, const cg_specs* s, const cg_zone* z, int64_t width,
+                    int32_t n_buckets, bool per_node = false, const cg_rules* rules = nullptr, int mode = 0) {
+  if (int rc = profile_check_args(fn, c, s, z, width, n_buckets)) return rc;
+  if (!per_node) return CG_OK;
+  if (!rules) return cg_fail(CG_EINVAL, std::string(fn) + ": null");
+  if (mode < 0 || mode > 2) return cg_fail(CG_EINVAL, "bad exclude mode");
+  if (int64_t(s->n) != rules->st.n_rules) return cg_fail(CG_EINVAL, "specs count != rules n_rules");
   return CG_OK;
 }
 
@@ -782,78 +740,74 @@ int profile_node_peaks_enqueue(cg_ctx* c) {
 extern "C" {
 
 int cg_profile_device(cg_ctx* c, const cg_specs* s, const cg_zone* z, int64_t t0, int64_t width, int32_t n_buckets) {
-  if (int rc = profile_check_args("cg_profile_device", c, s, z, width, n_buckets)) return rc;
-  return profile_call(c, s, z, t0, width, n_buckets, nullptr);
+  if (int rc = profile_prelude("cg_profile_device", c, s, z, width, n_buckets)) return rc;
+  return profile_call(c, s, z, t0, width, n_buckets, ProfileCall(), nullptr, 0);
 }
 
 int cg_profile_per_node_device(cg_ctx* c, const cg_specs* s, const cg_zone* z, int64_t t0, int64_t width,
                                int32_t n_buckets, const cg_rules* rules, int mode) {
-  if (int rc = profile_check_args("cg_profile_per_node_device", c, s, z, width, n_buckets)) return rc;
-  if (int rc = profile_check_node_args("cg_profile_per_node_device", s, rules, mode)) return rc;
-  return profile_per_node_call(c, s, z, t0, width, n_buckets, rules, mode, nullptr);
+  if (int rc = profile_prelude("cg_profile_per_node_device", c, s, z, width, n_buckets, true, rules, mode)) return rc;
+  return profile_call(c, s, z, t0, width, n_buckets, ProfileCall(), rules, mode);
 }
 
 int cg_inflight_device(cg_ctx* c, const cg_specs* s, const cg_zone* z, int64_t t0, int64_t width, int32_t n_buckets,
                        const int64_t* dur_ms) {
+  const char* fn = "cg_inflight_device";
   std::vector<int64_t> dsec;
-  if (int rc = profile_check_args("cg_inflight_device", c, s, z, width, n_buckets)) return rc;
-  if (int rc = inflight_durations("cg_inflight_device", s, dur_ms, int64_t(n_buckets) * width, &dsec)) return rc;
-  return profile_call(c, s, z, t0, width, n_buckets, &dsec);
+  if (int rc = profile_prelude(fn, c, s, z, width, n_buckets)) return rc;
+  if (int rc = inflight_durations(fn, s, dur_ms, int64_t(n_buckets) * width, &dsec)) return rc;
+  return profile_call(c, s, z, t0, width, n_buckets, ProfileCall::inflight(&dsec), nullptr, 0);
 }
 
 int cg_inflight_per_node_device(cg_ctx* c, const cg_specs* s, const cg_zone* z, int64_t t0, int64_t width,
                                 int32_t n_buckets, const int64_t* dur_ms, const cg_rules* rules, int mode) {
+  const char* fn = "cg_inflight_per_node_device";
   std::vector<int64_t> dsec;
-  if (int rc = profile_check_args("cg_inflight_per_node_device", c, s, z, width, n_buckets)) return rc;
-  if (int rc = profile_check_node_args("cg_inflight_per_node_device", s, rules, mode)) return rc;
-  if (int rc = inflight_durations("cg_inflight_per_node_device", s, dur_ms, int64_t(n_buckets) * width, &dsec))
-    return rc;
-  return profile_per_node_call(c, s, z, t0, width, n_buckets, rules, mode, &dsec);
+  if (int rc = profile_prelude(fn, c, s, z, width, n_buckets, true, rules, mode)) return rc;
+  if (int rc = inflight_durations(fn, s, dur_ms, int64_t(n_buckets) * width, &dsec)) return rc;
+  return profile_call(c, s, z, t0, width, n_buckets, ProfileCall::inflight(&dsec), rules, mode);
 }
 
 int cg_admit_device(cg_ctx* c, const cg_specs* s, const cg_zone* z, int64_t t0, int64_t width, int32_t n_buckets,
                     const int64_t* dur_ms, const int64_t* parallels, const int32_t* unit, int what) {
+  const char* fn = "cg_admit_device";
   AdmitCall adm;
-  if (int rc = profile_check_args("cg_admit_device", c, s, z, width, n_buckets)) return rc;
-  if (int rc = admit_units("cg_admit_device", s, dur_ms, parallels, unit, what, int64_t(n_buckets) * width, &adm))
-    return rc;
-  return profile_call(c, s, z, t0, width, n_buckets, adm.durations(), &adm);
+  if (int rc = profile_prelude(fn, c, s, z, width, n_buckets)) return rc;
+  if (int rc = admit_units(fn, s, dur_ms, parallels, unit, what, int64_t(n_buckets) * width, &adm)) return rc;
+  return profile_call(c, s, z, t0, width, n_buckets, ProfileCall::admission(&adm), nullptr, 0);
 }
 
 int cg_admit_per_node_device(cg_ctx* c, const cg_specs* s, const cg_zone* z, int64_t t0, int64_t width,
                              int32_t n_buckets, const int64_t* dur_ms, const int64_t* parallels,
                              const int32_t* unit, int what, const cg_rules* rules, int mode) {
+  const char* fn = "cg_admit_per_node_device";
   AdmitCall adm;
-  if (int rc = profile_check_args("cg_admit_per_node_device", c, s, z, width, n_buckets)) return rc;
-  if (int rc = profile_check_node_args("cg_admit_per_node_device", s, rules, mode)) return rc;
-  if (int rc = admit_units("cg_admit_per_node_device", s, dur_ms, parallels, unit, what, int64_t(n_buckets) * width,
-                           &adm))
-    return rc;
-  return profile_per_node_call(c, s, z, t0, width, n_buckets, rules, mode, adm.durations(), &adm);
+  if (int rc = profile_prelude(fn, c, s, z, width, n_buckets, true, rules, mode)) return rc;
+  if (int rc = admit_units(fn, s, dur_ms, parallels, unit, what, int64_t(n_buckets) * width, &adm)) return rc;
+  return profile_call(c, s, z, t0, width, n_buckets, ProfileCall::admission(&adm), rules, mode);
 }
 
 int cg_lock_profile_device(cg_ctx* c, const cg_specs* s, const cg_zone* z, int64_t t0, int64_t width,
                            int32_t n_buckets, const int32_t* kind, const int64_t* avg_time_ms, const int32_t* unit,
                            const uint8_t* contends, int64_t lock_ttl, int what) {
+  const char* fn = "cg_lock_profile_device";
   LockCall lk;
-  if (int rc = profile_check_args("cg_lock_profile_device", c, s, z, width, n_buckets)) return rc;
-  if (int rc = lock_units("cg_lock_profile_device", s, kind, avg_time_ms, unit, contends, lock_ttl, what,
-                          int64_t(n_buckets) * width, &lk))
+  if (int rc = profile_prelude(fn, c, s, z, width, n_buckets)) return rc;
+  if (int rc = lock_units(fn, s, kind, avg_time_ms, unit, contends, lock_ttl, what, int64_t(n_buckets) * width, &lk))
     return rc;
-  return profile_call(c, s, z, t0, width, n_buckets, lk.durations(), nullptr, &lk);
+  return profile_call(c, s, z, t0, width, n_buckets, ProfileCall::lock(&lk), nullptr, 0);
 }
 
 int cg_lock_profile_per_node_device(cg_ctx* c, const cg_specs* s, const cg_zone* z, int64_t t0, int64_t width,
                                     int32_t n_buckets, const int32_t* kind, const int64_t* avg_time_ms,
                                     const int32_t* unit, const uint8_t* contends, int64_t lock_ttl, int what,
                                     const cg_rules* rules, int mode) {
+  const char* fn = "cg_lock_profile_per_node_device";
   LockCall lk;
-  if (int rc = profile_check_args("cg_lock_profile_per_node_device", c, s, z, width, n_buckets)) return rc;
-  if (int rc = profile_check_node_args("cg_lock_profile_per_node_device", s, rules, mode)) return rc;
-  if (int rc = lock_units("cg_lock_profile_per_node_device", s, kind, avg_time_ms, unit, contends, lock_ttl, what,
-                          int64_t(n_buckets) * width, &lk))
+  if (int rc = profile_prelude(fn, c, s, z, width, n_buckets, true, rules, mode)) return rc;
+  if (int rc = lock_units(fn, s, kind, avg_time_ms, unit, contends, lock_ttl, what, int64_t(n_buckets) * width, &lk))
     return rc;
-  return profile_per_node_call(c, s, z, t0, width, n_buckets, rules, mode, lk.durations(), nullptr, &lk);
+  return profile_call(c, s, z, t0, width, n_buckets, ProfileCall::lock(&lk), rules, mode);
 }
 
 int cg_profile_kind(cg_ctx* c, int* kind) {

@@ -1,7 +1,9 @@
-// cg_units.h -- the checked per-rule arguments of an admission or a lock call:
-// what cg_admit_* / cg_lock_profile_* (cg_profile.hip) and the fire verdicts
-// (cg_verdict.hip) compact for their unit walks.  Host only; the checks, their
-// order, messages and codes are the same for every caller.
+// cg_units.h -- the host side of a unit walk, shared by cg_admit_* /
+// cg_lock_profile_* (cg_profile.hip) and the fire verdicts (cg_verdict.hip):
+// the checked per-rule arguments of an admission or a lock call, compacted into
+// units; their upload; the LDS-budget refusals and the stuck-rule message.  Host
+// only (the kernels' side is cg_unit_walk.h); the checks, their order, messages
+// and codes are the same for every caller.
 #pragma once
 #include <algorithm>
 #include <string>
@@ -12,6 +14,7 @@
 #include "cg_api_internal.h"
 #include "cg_lock.h"
 #include "cg_profile.h"
+#include "cg_unit_walk.h"
 
 // An admission call's checked arguments: the units that can drop, compacted,
 // and per rule whether its unit is one of them.  Host memory that outlives the
@@ -135,4 +138,70 @@ inline int lock_units(const char* what_fn, const cg_specs* s, const int32_t* kin
     r0 = r1;
   }
   return CG_OK;
+}
+
+// Uploads a call's units and flags into the ctx's shared buffers (uw_*, slot 0
+// admission, slot 1 lock; adm / lk null: none of that kind) on the ctx stream
+// and, with err, sets both error words to ~0.  flag0: slot 0's flags when they
+// are not adm's own (a verdict call's initial bytes).  The host arrays must
+// outlive the stream synchronise that ends the call; c->mu held.
+inline int unit_upload(cg_ctx* c, int64_t R, const AdmitCall* adm, const LockCall* lk, const uint8_t* flag0,
+                       bool err) {
+  using namespace cg;
+  static_assert(sizeof(AdmitUnit) == 24 && sizeof(LockUnit) == 32, "units are uploaded as packed records");
+  hipStream_t st = c->st;
+  int rc;
+  if (adm && !flag0) flag0 = adm->flag.data();
+  if (flag0) {
+    if ((rc = c->uw_flag[0].ensure(size_t(R)))) return rc;
+    HIPCHK(hipMemcpyAsync(c->uw_flag[0].p, flag0, size_t(R), hipMemcpyHostToDevice, st));
+  }
+  if (adm) {
+    const size_t bytes = adm->units.size() * sizeof(AdmitUnit);
+    if ((rc = c->uw_units[0].ensure(std::max<size_t>(bytes, 1)))) return rc;
+    if (bytes) HIPCHK(hipMemcpyAsync(c->uw_units[0].p, adm->units.data(), bytes, hipMemcpyHostToDevice, st));
+  }
+  if (lk) {
+    const size_t bytes = lk->units.size() * sizeof(LockUnit);
+    if ((rc = c->uw_flag[1].ensure(size_t(R))) || (rc = c->uw_units[1].ensure(std::max<size_t>(bytes, 1)))) return rc;
+    HIPCHK(hipMemcpyAsync(c->uw_flag[1].p, lk->flag.data(), size_t(R), hipMemcpyHostToDevice, st));
+    if (bytes) HIPCHK(hipMemcpyAsync(c->uw_units[1].p, lk->units.data(), bytes, hipMemcpyHostToDevice, st));
+  }
+  if (err) {
+    if ((rc = c->uw_err.ensure(2))) return rc;
+    HIPCHK(hipMemsetAsync(c->uw_err.p, 0xFF, 2 * sizeof(unsigned long long), st));
+  }
+  return CG_OK;
+}
+inline const cg::AdmitUnit* uw_admit_units(const cg_ctx* c) {
+  return reinterpret_cast<const cg::AdmitUnit*>(c->uw_units[0].p);
+}
+inline const cg::LockUnit* uw_lock_units(const cg_ctx* c) {
+  return reinterpret_cast<const cg::LockUnit*>(c->uw_units[1].p);
+}
+
+// the error words behind the walks: copied back, the stream drained
+inline int unit_errors(cg_ctx* c, unsigned long long err[2]) {
+  err[0] = err[1] = ~0ULL;
+  HIPCHK(hipMemcpyAsync(err, c->uw_err.p, 2 * sizeof(unsigned long long), hipMemcpyDeviceToHost, c->st));
+  HIPCHK(hipStreamSynchronize(c->st));
+  return CG_OK;
+}
+
+// a walk's launch must fit the 64 KiB of LDS behind the staged plan
+inline int admit_lds_check(const char* fn, size_t plan_lds) {
+  if (cg::admit_lds_bytes(plan_lds) <= 64 * 1024) return CG_OK;
+  return cg_fail(CG_ERANGE, std::string(fn) + ": the plan of this horizon leaves no LDS for the admission ring");
+}
+inline int lock_lds_check(const char* fn, size_t plan_lds) {
+  if (cg::lock_lds_bytes(plan_lds) <= 64 * 1024) return CG_OK;
+  return cg_fail(CG_ERANGE,
+                 std::string(fn) + ": the plan of this horizon leaves no LDS for the walked runs' positions");
+}
+// a granted fire whose Next never returns: the reference hangs in lockTtl
+// there, and the unit's rows or bytes are unfinished
+inline std::string lock_stuck_msg(const char* fn, unsigned long long rule) {
+  return std::string(fn) + ": rule " + std::to_string(rule) +
+         ": Next never returns from a fire of this horizon that finds the lock free "
+         "(the reference's lockTtl does not return there)";
 }

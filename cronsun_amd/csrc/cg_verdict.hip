@@ -9,12 +9,11 @@
 //                      "unit can drop", bit 1 "contending rule of a lock unit");
 //                      16 bytes per lane, a tile's rule range found by search
 //                      over the rule offsets
-//   k_admit_verdicts   k_admit_units' layout: one lane per unit that can drop
-//                      walks the unit's admitted fires (cg_admit.h) and clears
-//                      bit 0 at fire_position (cg_verdict.h)
-//   k_lock_verdicts    k_lock_units' layout: one lane per lock unit with a
-//                      contending rule walks the granted fires (cg_lock.h) and
-//                      clears bit 1
+//   k_admit_verdicts   k_admit_units' lane body (cg_unit_walk.h): one lane per
+//                      unit that can drop walks the unit's admitted fires and
+//                      clears bit 0 at fire_position (cg_verdict.h)
+//   k_lock_verdicts    k_lock_units' lane body: one lane per lock unit with a
+//                      contending rule walks the granted fires and clears bit 1
 //   k_verdict_count    one wave per rule: fires with (v & mask) == value
 //   launch_scan        their exclusive scan: sel_off [R+1]
 //   k_verdict_select   one wave per rule: the matching fires' times, in order,
@@ -30,10 +29,8 @@
 #include <string>
 
 #include "../../include/cronsun_gpu.h"
-#include "cg_admit.h"
 #include "cg_api_internal.h"
-#include "cg_lock.h"
-#include "cg_stage.h"
+#include "cg_unit_walk.h"
 #include "cg_units.h"
 #include "cg_verdict.h"
 
@@ -43,7 +40,6 @@ namespace {
 
 static_assert(kVerdictDropped == CG_VERDICT_DROPPED && kVerdictSkipped == CG_VERDICT_SKIPPED,
               "cg_verdict.h and the public header disagree");
-static_assert(sizeof(AdmitUnit) == 24 && sizeof(LockUnit) == 32, "units are uploaded as packed records");
 
 // ---------------------------------------------------------------- init pass --
 // largest r in [lo, hi] with off[r] <= e: the rule of fire index e when the
@@ -128,54 +124,30 @@ __device__ __forceinline__ void clear_verdict(const VerdictOut& o, const DSpec* 
   o.verdict[pos] &= uint8_t(~bit);
 }
 
-// k_admit_units' layout (cg_profile.hip): a block is one wave, one lane per
-// compacted unit; ring and walk cache in LDS behind the staged plan,
-// [slot][lane]
-constexpr int kAdmitBlock = 64;
-__global__ __launch_bounds__(kAdmitBlock) void k_admit_verdicts(const DSpec* __restrict__ specs, PlanArgs p,
-                                                                 const int64_t* __restrict__ run_anchor,
-                                                                 const int32_t* __restrict__ run_count,
-                                                                 const uint32_t* __restrict__ run_dmask,
-                                                                 const AdmitUnit* __restrict__ units, int64_t U,
-                                                                 size_t ring_off, VerdictOut o) {
-  extern __shared__ __align__(16) char lds[];
-  PlanView v = stage_plan(p, lds);
-  int64_t* ring = reinterpret_cast<int64_t*>(lds + ring_off) + threadIdx.x;
-  int32_t* w32 = reinterpret_cast<int32_t*>(ring - threadIdx.x + (kAdmitMaxParallels + kAdmitWalkSlots) * kAdmitBlock) +
-                 threadIdx.x;
-  const AdmitWalkCache wc{ring + kAdmitMaxParallels * kAdmitBlock, w32, w32 + kAdmitWalkSlots * kAdmitBlock,
-                          w32 + 2 * kAdmitWalkSlots * kAdmitBlock, kAdmitBlock};
-  const int64_t i = blockIdx.x * int64_t(kAdmitBlock) + threadIdx.x;
-  if (i >= U) return;
-  const AdmitUnit u = units[i];
-  admit_walk_unit(specs, v.z, v.segs, p.G, run_anchor, run_count, run_dmask, p.t0, p.t1, u, ring, kAdmitBlock, wc,
-                  [&](int64_t r, int64_t t) {
+// the walks of k_admit_units / k_lock_units (cg_unit_walk.h) with the clearing
+// emit; a rule whose Next never returns lowers err[1] to its index
+__global__ __launch_bounds__(kUnitBlock) void k_admit_verdicts(const DSpec* __restrict__ specs, PlanArgs p,
+                                                                const int64_t* __restrict__ run_anchor,
+                                                                const int32_t* __restrict__ run_count,
+                                                                const uint32_t* __restrict__ run_dmask,
+                                                                const AdmitUnit* __restrict__ units, int64_t U,
+                                                                size_t ring_off, VerdictOut o) {
+  admit_unit_lane(specs, p, run_anchor, run_count, run_dmask, units, U, ring_off,
+                  [&](const PlanView& v, const AdmitUnit&, int64_t r, int64_t t) {
                     clear_verdict(o, specs, v.segs, p.G, run_anchor, run_count, run_dmask, p.t1, r, t,
                                   kVerdictDropped);
                   });
 }
 
-// k_lock_units' layout: the walk cache alone in LDS; a rule whose Next never
-// returns lowers err[1] to its index
-constexpr int kLockBlock = 64;
-__global__ __launch_bounds__(kLockBlock) void k_lock_verdicts(const DSpec* __restrict__ specs, PlanArgs p,
+__global__ __launch_bounds__(kUnitBlock) void k_lock_verdicts(const DSpec* __restrict__ specs, PlanArgs p,
                                                                const int64_t* __restrict__ run_anchor,
                                                                const int32_t* __restrict__ run_count,
                                                                const uint32_t* __restrict__ run_dmask,
                                                                const LockUnit* __restrict__ units, int64_t U,
                                                                const uint8_t* __restrict__ contends, size_t cache_off,
                                                                int64_t lock_ttl, VerdictOut o) {
-  extern __shared__ __align__(16) char lds[];
-  PlanView v = stage_plan(p, lds);
-  int64_t* wt = reinterpret_cast<int64_t*>(lds + cache_off) + threadIdx.x;
-  int32_t* w32 = reinterpret_cast<int32_t*>(lds + cache_off + size_t(kAdmitWalkSlots) * kLockBlock * 8) + threadIdx.x;
-  const AdmitWalkCache wc{wt, w32, w32 + kAdmitWalkSlots * kLockBlock, w32 + 2 * kAdmitWalkSlots * kLockBlock,
-                          kLockBlock};
-  const int64_t i = blockIdx.x * int64_t(kLockBlock) + threadIdx.x;
-  if (i >= U) return;
-  const LockUnit u = units[i];
-  const int64_t bad = lock_walk_unit(specs, v.z, v.segs, p.G, run_anchor, run_count, run_dmask, p.t0, p.t1, u,
-                                     lock_ttl, contends, wc, [&](int64_t r, int64_t t) {
+  const int64_t bad = lock_unit_lane(specs, p, run_anchor, run_count, run_dmask, units, U, cache_off, contends,
+                                     lock_ttl, [&](const PlanView& v, const LockUnit&, int64_t r, int64_t t) {
                                        clear_verdict(o, specs, v.segs, p.G, run_anchor, run_count, run_dmask, p.t1,
                                                      r, t, kVerdictSkipped);
                                      });
@@ -220,12 +192,6 @@ __global__ __launch_bounds__(256) void k_verdict_select(const int64_t* __restric
 }
 
 // --------------------------------------------------------------------- host --
-int ensure_events(cg_ctx* c) {
-  for (hipEvent_t& e : c->vdev)
-    if (!e) HIPCHK(hipEventCreateWithFlags(&e, hipEventDisableSystemFence));
-  return CG_OK;
-}
-
 int no_verdicts() {
   return cg_fail(CG_EINVAL, "no fire verdicts (no verdict call has succeeded, or a later expansion call replaced "
                             "the result they belong to)");
@@ -242,75 +208,49 @@ int verdicts_locked(cg_ctx* c, const cg_specs* s, const cg_zone* z, int64_t t0, 
   for (float& x : c->vd_ms) x = 0.f;
   HIPCHK(hipSetDevice(c->device));
   int rc;
-  if ((rc = ensure_events(c))) return rc;
+  if ((rc = ensure_events(c->vdev))) return rc;
   hipStream_t st = c->st;
   // the plain expansion; a lock call's count chain stages the lock table
-  (void)hipEventRecord(c->vdev[0], st);
+  (void)hipEventRecord(c->vdev[VDEV_EXPAND], st);
   int64_t E = 0;
   if ((rc = expand_device_locked(c, s, z, t0, t1, &E, lk != nullptr))) return rc;
-  for (int i = 1; i < 5; i++) (void)hipEventRecord(c->vdev[i], st);
+  for (int i = VDEV_INIT; i <= VDEV_WALKS_END; i++) (void)hipEventRecord(c->vdev[i], st);
   const int64_t R = int64_t(s->n);
   RunSet& rs = c->rs;
   if ((rc = c->vd_verdict.ensure(size_t(std::max<int64_t>(E, 1))))) return rc;
   if (E > 0) {
+    const char* fn = "cg_expand_verdicts_device";
     const int64_t UA = adm ? int64_t(adm->units.size()) : 0, UL = lk ? int64_t(lk->units.size()) : 0;
-    const size_t lds = plan_lds_bytes(rs.pa);
-    const size_t tail_off = align_up(lds, 16);
-    const size_t admit_lds = tail_off + size_t(kAdmitBlock) * kAdmitLaneBytes;
-    const size_t lock_lds = tail_off + size_t(kLockBlock) * kLockLaneBytes;
-    if (UA > 0 && admit_lds > 64 * 1024)
-      return cg_fail(CG_ERANGE, "cg_expand_verdicts_device: the plan of this horizon leaves no LDS for the admission ring");
-    if (UL > 0 && lock_lds > 64 * 1024)
-      return cg_fail(CG_ERANGE, "cg_expand_verdicts_device: the plan of this horizon leaves no LDS for the walked "
-                                "runs' positions");
-    // (flag, the units and the lock flags are the caller's host memory, which
-    // outlives the stream synchronise that ends the call on every path)
-    if ((rc = c->vd_flag.ensure(size_t(R))) || (rc = c->vd_err.ensure(2))) return rc;
-    HIPCHK(hipMemcpyAsync(c->vd_flag.p, flag.data(), size_t(R), hipMemcpyHostToDevice, st));
-    HIPCHK(hipMemsetAsync(c->vd_err.p, 0xFF, 2 * sizeof(unsigned long long), st));
-    if (UA > 0) {
-      if ((rc = c->vd_admit_units.ensure(size_t(UA) * sizeof(AdmitUnit)))) return rc;
-      HIPCHK(hipMemcpyAsync(c->vd_admit_units.p, adm->units.data(), size_t(UA) * sizeof(AdmitUnit),
-                            hipMemcpyHostToDevice, st));
-    }
-    if (UL > 0) {
-      if ((rc = c->vd_lock_units.ensure(size_t(UL) * sizeof(LockUnit))) || (rc = c->vd_contends.ensure(size_t(R))))
-        return rc;
-      HIPCHK(hipMemcpyAsync(c->vd_lock_units.p, lk->units.data(), size_t(UL) * sizeof(LockUnit),
-                            hipMemcpyHostToDevice, st));
-      HIPCHK(hipMemcpyAsync(c->vd_contends.p, lk->flag.data(), size_t(R), hipMemcpyHostToDevice, st));
-    }
-    const VerdictOut o{rs.run_off.p, c->times.p, c->vd_verdict.p, E, c->vd_err.p};
-    (void)hipEventRecord(c->vdev[1], st);
+    const size_t lds = plan_lds_bytes(rs.pa), tail_off = unit_tail_off(lds);
+    if ((UA > 0 && (rc = admit_lds_check(fn, lds))) || (UL > 0 && (rc = lock_lds_check(fn, lds)))) return rc;
+    if ((rc = unit_upload(c, R, UA > 0 ? adm : nullptr, UL > 0 ? lk : nullptr, flag.data(), true))) return rc;
+    const VerdictOut o{rs.run_off.p, c->times.p, c->vd_verdict.p, E, c->uw_err.p};
+    (void)hipEventRecord(c->vdev[VDEV_INIT], st);
     hipLaunchKernelGGL(k_verdict_init, dim3(gridn(E, kInitTile, 1 << 16)), dim3(256), 0, st, rs.offsets.p, R, E,
-                       c->vd_flag.p, c->vd_verdict.p);
-    (void)hipEventRecord(c->vdev[2], st);
+                       c->uw_flag[0].p, c->vd_verdict.p);
+    (void)hipEventRecord(c->vdev[VDEV_ADMIT], st);
     if (UA > 0)
-      hipLaunchKernelGGL(k_admit_verdicts, dim3(unsigned((UA + kAdmitBlock - 1) / kAdmitBlock)), dim3(kAdmitBlock),
-                         admit_lds, st, s->d, rs.pa, rs.run_anchor.p, rs.run_count.p, rs.run_dmask.p,
-                         reinterpret_cast<const AdmitUnit*>(c->vd_admit_units.p), UA, tail_off, o);
-    (void)hipEventRecord(c->vdev[3], st);
+      hipLaunchKernelGGL(k_admit_verdicts, dim3(unsigned((UA + kUnitBlock - 1) / kUnitBlock)), dim3(kUnitBlock),
+                         admit_lds_bytes(lds), st, s->d, rs.pa, rs.run_anchor.p, rs.run_count.p, rs.run_dmask.p,
+                         uw_admit_units(c), UA, tail_off, o);
+    (void)hipEventRecord(c->vdev[VDEV_LOCK], st);
     if (UL > 0)
-      hipLaunchKernelGGL(k_lock_verdicts, dim3(unsigned((UL + kLockBlock - 1) / kLockBlock)), dim3(kLockBlock),
-                         lock_lds, st, s->d, rs.pa, rs.run_anchor.p, rs.run_count.p, rs.run_dmask.p,
-                         reinterpret_cast<const LockUnit*>(c->vd_lock_units.p), UL, c->vd_contends.p, tail_off,
-                         lk->lock_ttl, o);
-    (void)hipEventRecord(c->vdev[4], st);
+      hipLaunchKernelGGL(k_lock_verdicts, dim3(unsigned((UL + kUnitBlock - 1) / kUnitBlock)), dim3(kUnitBlock),
+                         lock_lds_bytes(lds), st, s->d, rs.pa, rs.run_anchor.p, rs.run_count.p, rs.run_dmask.p,
+                         uw_lock_units(c), UL, c->uw_flag[1].p, tail_off, lk->lock_ttl, o);
+    (void)hipEventRecord(c->vdev[VDEV_WALKS_END], st);
     HIPCHK(hipGetLastError());
-    unsigned long long err[2] = {~0ULL, ~0ULL};
-    HIPCHK(hipMemcpyAsync(err, c->vd_err.p, sizeof err, hipMemcpyDeviceToHost, st));
-    HIPCHK(hipStreamSynchronize(st));
-    if (err[1] != ~0ULL)
-      return cg_fail(CG_ERANGE, "cg_expand_verdicts_device: rule " + std::to_string(err[1]) +
-                                    ": Next never returns from a fire of this horizon that finds the lock free "
-                                    "(the reference's lockTtl does not return there)");
+    unsigned long long err[2];
+    if ((rc = unit_errors(c, err))) return rc;
+    if (err[1] != ~0ULL) return cg_fail(CG_ERANGE, lock_stuck_msg(fn, err[1]));
     if (err[0] != ~0ULL)
       return cg_fail(CG_EHIP, "verdict position mismatch: rule " + std::to_string(err[0]) +
                                   ": a fire of the unit walk is not where fire_position puts it in the result");
   } else {
     HIPCHK(hipStreamSynchronize(st));
   }
-  for (int i = 0; i < 4; i++) (void)hipEventElapsedTime(&c->vd_ms[i], c->vdev[i], c->vdev[i + 1]);
+  for (int i = VDEV_EXPAND; i < VDEV_WALKS_END; i++)
+    (void)hipEventElapsedTime(&c->vd_ms[i], c->vdev[i], c->vdev[i + 1]);
   c->vd_R = R;
   c->vd_E = E;
   c->vd_gen = c->res_gen;
@@ -386,7 +326,7 @@ int cg_verdicts_select_device(cg_ctx* c, int mask, int value, int64_t* n_selecte
   (void)hipGetLastError();
   HIPCHK(hipSetDevice(c->device));
   int rc;
-  if ((rc = ensure_events(c))) return rc;
+  if ((rc = ensure_events(c->vdev))) return rc;
   hipStream_t st = c->st;
   const int64_t R = c->vd_R;
   c->vd_ms[4] = c->vd_ms[5] = 0.f;
@@ -400,25 +340,25 @@ int cg_verdicts_select_device(cg_ctx* c, int mask, int value, int64_t* n_selecte
     if ((rc = c->vd_sel_times.ensure(1))) return rc;
   } else {
     const int64_t* off = c->rs.offsets.p;
-    (void)hipEventRecord(c->vdev[5], st);
+    (void)hipEventRecord(c->vdev[VDEV_SEL_COUNT], st);
     hipLaunchKernelGGL(k_verdict_count, dim3(gridn(R, 4, 1 << 16)), dim3(256), 0, st, off, R, c->vd_verdict.p,
                        uint32_t(mask), uint32_t(value), c->vd_sel_cnt.p);
     launch_scan(c->vd_sel_cnt.p, c->vd_sel_off.p, R, c->scan_tmp.p, st);
-    (void)hipEventRecord(c->vdev[6], st);
+    (void)hipEventRecord(c->vdev[VDEV_SELECT], st);
     HIPCHK(hipGetLastError());
     HIPCHK(hipMemcpyAsync(&n, c->vd_sel_off.p + R, 8, hipMemcpyDeviceToHost, st));
     HIPCHK(hipStreamSynchronize(st));
-    (void)hipEventElapsedTime(&c->vd_ms[4], c->vdev[5], c->vdev[6]);
+    (void)hipEventElapsedTime(&c->vd_ms[4], c->vdev[VDEV_SEL_COUNT], c->vdev[VDEV_SELECT]);
     if (n < 0 || n > c->vd_E) return cg_fail(CG_EHIP, "cg_verdicts_select_device: selection count out of range");
     if ((rc = c->vd_sel_times.ensure(size_t(std::max<int64_t>(n, 1))))) return rc;
-    (void)hipEventRecord(c->vdev[6], st);
+    (void)hipEventRecord(c->vdev[VDEV_SELECT], st);
     if (n > 0)
       hipLaunchKernelGGL(k_verdict_select, dim3(gridn(R, 4, 1 << 16)), dim3(256), 0, st, off, R, c->vd_verdict.p,
                          c->times.p, uint32_t(mask), uint32_t(value), c->vd_sel_off.p, c->vd_sel_times.p);
-    (void)hipEventRecord(c->vdev[7], st);
+    (void)hipEventRecord(c->vdev[VDEV_SELECT_END], st);
     HIPCHK(hipGetLastError());
     HIPCHK(hipStreamSynchronize(st));
-    (void)hipEventElapsedTime(&c->vd_ms[5], c->vdev[6], c->vdev[7]);
+    (void)hipEventElapsedTime(&c->vd_ms[5], c->vdev[VDEV_SELECT], c->vdev[VDEV_SELECT_END]);
   }
   c->vd_nsel = n;
   c->vd_sel_valid = true;

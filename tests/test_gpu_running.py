@@ -340,3 +340,83 @@ def test_state_between_calls_and_refusals(eng):
     rules, totals = eng.admit(sp.slice(0, 0), None, c.t0, c.w, 24, [], [], None, what="running")
     assert rules.shape == (0, 24) and not totals.any() and eng.profile_kind() == _lib.PROFILE_RUNNING
     sp.free()
+
+
+# ------------------------------------------- the unit walks' shared uploads --
+def _shared_upload_sets():
+    """Two rule sets off the builders above.  Small: the first 37 rules in their
+    units (a single partial wave of units).  Large: the first 300 rules, every
+    rule its own unit (more than one block of units, the last one partial)."""
+    specs, (kind, avg, lunit, contends) = GA.the_specs(), GL.unit_args()
+    sets = {}
+    for name, R, grouped in (("small", 37, True), ("large", 300, False)):
+        sets[name] = dict(specs=specs[:R], grouped=grouped, kind=kind[:R].copy(), avg=avg[:R].copy(),
+                          lunit=lunit[:R].copy() if grouped else None, contends=contends[:R].copy())
+    return sets
+
+
+def _unit_counts(s, w, B):
+    """(units that can drop, lock units with a contending rule) of a set."""
+    R = len(s["specs"])
+    dur, par, unit = (x[:R] for x in unit_args(w, B))
+    ids = unit if s["grouped"] else np.arange(R)
+    d = np.minimum(IM.seconds(dur), w * B)
+    drop = lock = 0
+    for u in np.unique(ids):
+        rows = np.nonzero(ids == u)[0]
+        drop += not AM.never_drops(int(par[rows[0]]), int(d[rows[0]]), len(rows))
+        lock += bool(s["kind"][rows[0]] != GL.C_ and s["contends"][rows].any())
+    return drop, lock
+
+
+def _shared_upload_call(eng, s, what, w, B):
+    """One call on set s, its arrays copied to the host: a tuple of arrays."""
+    R = len(s["specs"])
+    sp = upload(eng, s["specs"])
+    dur, par, unit = (x[:R].copy() for x in unit_args(w, B))
+    if not s["grouped"]:
+        unit = None
+    t0 = PC.T0_UTC
+    if what.startswith("admit"):
+        out = eng.admit(sp, None, t0, w, B, dur, par, unit, what=what[6:])
+    elif what.startswith("lock"):
+        out = eng.lock_runs(sp, None, t0, w, B, s["kind"], s["avg"], s["lunit"], s["contends"], 300, what=what[5:])
+    else:
+        out = eng.expand_verdicts(sp, None, t0, t0 + 3600, (dur, par, unit),
+                                  (s["kind"], s["avg"], s["lunit"], s["contends"], 300))
+    sp.free()
+    return tuple(np.array(x) for x in out)
+
+
+def test_unit_uploads_shared_between_kinds_and_sets():
+    """The profile and the verdict calls upload their units, flags and error
+    words into one set of buffers: on one engine, calls of every kind
+    interleaved over a small and a large rule set -- so the buffers grow and
+    are then reused by another kind with fewer units -- each give what the same
+    call gives as the first call of a fresh engine.  One hour in UTC; B = 5 and
+    B = 70, either side of the 64-lane tile switch and no power of two."""
+    from cronsun_amd.engine import Engine
+    sets = _shared_upload_sets()
+    shapes = {5: 720, 70: 51}  # B: w, at most one hour
+    for B, w in shapes.items():
+        drop, lock = _unit_counts(sets["small"], w, B)
+        assert 0 < drop < 64 and 0 < lock < 64, (B, drop, lock)
+        drop, lock = _unit_counts(sets["large"], w, B)
+        assert drop > 64 and drop % 64 and lock > 64 and lock % 64, (B, drop, lock)
+    calls = [("small", "admit.dropped", 5), ("large", "lock.skipped", 70), ("small", "verdicts", 70),
+             ("large", "admit.running", 70), ("small", "lock.running", 5), ("large", "verdicts", 5),
+             ("small", "admit.running", 70), ("large", "admit.dropped", 5), ("small", "lock.skipped", 70),
+             ("large", "lock.running", 5), ("small", "verdicts", 5)]
+    exp = []
+    for name, what, B in calls:
+        fresh = Engine(0)
+        exp.append(_shared_upload_call(fresh, sets[name], what, shapes[B], B))
+        fresh.close()
+    one = Engine(0)
+    for (name, what, B), e in zip(calls, exp):
+        got = _shared_upload_call(one, sets[name], what, shapes[B], B)
+        assert len(got) == len(e)
+        for i, (g, x) in enumerate(zip(got, e)):
+            assert g.dtype == x.dtype and np.array_equal(g, x), (name, what, B, i)
+        assert any(x.any() for x in e[-1:]), (name, what, B)  # the kind's own output is not all zero
+    one.close()
